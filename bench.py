@@ -15,7 +15,10 @@ contiguous row ranges balanced by pair count and never communicate on the comput
   c3  configs[3]   50,000 x 1,000 all pairs, 1.25e9 pairs      STRONG: the fixed problem sharded over N GPUs
   c4  configs[4]   1,000,000 x 2,000, 500 kb window, 1 kb gaps STRONG (48 GB matrix; --sites scales it down)
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Beside the contract's fields:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints
+that line: the headline, the kernel-time roofline of the timed launches, the ranks' checksums.  --dump-outputs DIR also writes
+the records of the last timed step (a fixed, seeded sample of them) as .npy files, so that two builds can be compared output for
+output.  The legs below take runs of their own and come with --full only (null otherwise):
   value_host_resident  SURVEY §8(d)'s metric to the letter: pairs / wall time from the first kernel launch to the last
                        record resident in HOST memory (ngsld_run: kernel || D2H into pinned buffers || sink), all ranks
   e2e_file_to_tsv_s    N = 1, configs[2]: the drop-in binary, binary GL file in -> TSV text out (to /dev/null)
@@ -28,6 +31,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement).  Beside the con
                        file of the sample's first sites to TSV; beside it `port` = the oracle restatement (whole per-pair path,
                        with the whole-sample parity check against the GPU's records) and `reference` = the reference's
                        compiled haplo_freq alone (the EM only), each also on one thread
+  unfiltered_input, other_configs, replay_off, roofline.traffic (rocprofv3 --pmc passes; from profiles/hbm_traffic.json
+                       without --full)
 """
 from __future__ import annotations
 
@@ -47,6 +52,7 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_PEAK_TFLOPS = 78.6    # MI355X FP64 vector peak
 STD_BYTES, EXT_BYTES = 32, 40
+DUMP_PAIRS, DUMP_SEED = 1 << 19, 20240521   # --dump-outputs: at most this many records (88 B each as float64: 44 MiB), all ranks
 
 CONFIGS = {  # sites (per GPU when weak, total when strong), ind, max_kb, max_gap, scaling, steps, warmup
     "c1": dict(sites=5_000, ind=100, max_kb=0, max_gap=200, scaling="weak", steps=5, warmup=2,
@@ -74,6 +80,12 @@ def parse():
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--pairs-per-item", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (cpu_baseline, host-resident, file -> TSV, unfiltered input, other "
+                         "configs, replay off, rocprofv3 traffic); the --no-* options below leave out single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last one (a fixed, seeded sample of at most "
+                         f"{DUMP_PAIRS} pairs) as DIR/<field>.npy, float64")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of each cpu_baseline leg")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-sink", action="store_true", help="skip the host-resident leg (value_host_resident)")
@@ -107,6 +119,10 @@ def parse():
     for k in ("steps", "warmup", "sites", "ind", "max_kb", "max_gap", "scaling"):
         if getattr(a, k) is None:
             setattr(a, k, preset[k])
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.native_multi:
+        ap.error("--dump-outputs: --native-multi hands its records to a discarding sink; there is nothing to write")
     return a
 
 
@@ -622,6 +638,29 @@ def native_multi(args) -> None:
     print(json.dumps(out), flush=True)
 
 
+def dump_outputs(out_dir: str, d_std, d_ext, n_pairs: int, rank: int, world: int) -> None:
+    """--dump-outputs: the records of the last timed step as a caller of ngsld_run_device receives them (capi.REC_STD and
+    capi.REC_EXT, in plan order), one float64 .npy per field: r2_ExpG, D, Dp, r2, hap (pairs x 4), n_ind_data, n_iter, and
+    pair_index, the records' positions in the step's output.  Above DUMP_PAIRS / world records, a sample drawn with DUMP_SEED:
+    the same records for the same arguments.  With several ranks every rank writes its own files (<field>_rank<k>.npy)."""
+    import torch
+    from ngsld_amd import capi
+    k = min(n_pairs, DUMP_PAIRS // world)
+    idx = np.arange(n_pairs, dtype=np.int64)
+    if k < n_pairs:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pairs, size=k, replace=False)).astype(np.int64)
+    at = torch.from_numpy(idx).to(d_std.device)
+    std = d_std.view(torch.float64).view(-1, STD_BYTES // 8)[at].cpu().numpy()
+    hap = d_ext.view(torch.float64).view(-1, EXT_BYTES // 8)[at, :4].cpu().numpy()
+    counts = d_ext.view(torch.int32).view(-1, EXT_BYTES // 4)[at, 8:10].cpu().numpy().view(np.uint32)
+    fields = {name: std[:, j] for j, name in enumerate(capi.REC_STD.names)}
+    fields.update(hap=hap, n_ind_data=counts[:, 0], n_iter=counts[:, 1], pair_index=idx)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.native_multi:
@@ -731,11 +770,11 @@ def main():
     headline = world == 1 and not args.ignore_miss and args.rnd_sample >= 1.0 and not args.hard_calls and not uncalled
     raw_head = None
     family = eng.pair_kernel()
-    if rank == 0 and headline and not args.no_cpu:
+    if rank == 0 and headline and args.full and not args.no_cpu:
         head = min(n_sites, 12_000 if n_ind <= 500 else 6_000)
         raw_head = raw[:head].cpu().numpy()
     e2e = None
-    if rank == 0 and headline and not args.no_e2e and args.config == "c2" and not args.custom:
+    if rank == 0 and headline and args.full and not args.no_e2e and args.config == "c2" and not args.custom:
         torch.cuda.synchronize()
         e2e = e2e_file_to_tsv(raw, n_sites, n_ind, chrs, pos, args.max_kb, host_cpus()["threads_used"])
         if e2e is not None and "seconds" in e2e and not args.no_unfiltered:
@@ -748,13 +787,13 @@ def main():
             torch.cuda.empty_cache()
     unfiltered = None
     profiled = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER", "ROCTX")) for k in os.environ)  # (its kernels would land in the profile)
-    if rank == 0 and headline and not args.no_unfiltered and args.config == "c2" and not args.custom and not profiled:
+    if rank == 0 and headline and args.full and not args.no_unfiltered and args.config == "c2" and not args.custom and not profiled:
         unfiltered = unfiltered_input_leg(10_000, n_ind, args.max_kb, args.max_gap, args.depth, dev_index,
                                           full_sites=args.sites if args.sites >= 50_000 else 0)
     del slab, raw
     torch.cuda.empty_cache()
     other_configs = None
-    if rank == 0 and headline and not args.no_other_configs and args.config == "c2" and not args.custom and not profiled:
+    if rank == 0 and headline and args.full and not args.no_other_configs and args.config == "c2" and not args.custom and not profiled:
         other_configs = other_configs_leg(dev_index, args.depth, args.seed)
 
     d_std = torch.empty(max(n_pairs, 1) * STD_BYTES, dtype=torch.uint8, device=dev)
@@ -797,10 +836,12 @@ def main():
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_std, d_ext, n_pairs, rank, world)
 
     replay_info = eng.replay_info()
     replay_off = None
-    if uncalled and world == 1:          # the same pass with the exact-order replay off: what the replay costs on this input
+    if args.full and uncalled and world == 1:   # the same pass with the exact-order replay off: what the replay costs on this input
         eng.set_replay(False)
         eng.plan(max_kb_dist=args.max_kb, extend_out=True, ignore_miss_data=args.ignore_miss, rnd_sample=args.rnd_sample, seed=12345)
         step()
@@ -816,7 +857,7 @@ def main():
 
     # ---- SURVEY §8(d)'s metric to the letter: last record resident in HOST memory (kernel || D2H || sink) ----
     sink_elapsed, sink_passes = 0.0, max(1, min(args.steps, 3))
-    if not args.no_sink:
+    if args.full and not args.no_sink:
         eng.run_discard(0, n_rows)                               # warm-up pass: pinned buffers, host copy of the plan
         torch.cuda.synchronize()
         barrier()
@@ -881,7 +922,7 @@ def main():
             "metric": f"SNP-pair EM-LD computations/sec @ n_ind={n_ind}", "value": value, "unit": "pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed_max / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"synthetic binary GL, {args.sites} sites{'' if strong else '/GPU'} x {n_ind} ind, depth {args.depth:g}, "
                                    f"--max_kb_dist {args.max_kb} {'windowed' if args.max_kb else 'all pairs'}, --extend_out"
                                    + (", hard-called" if args.hard_calls else "")
@@ -944,7 +985,7 @@ def main():
         traffic, traffic_src, traffic_detail = None, None, None
         launches_per_step = max(launches, 1) / max(args.steps, 1)
         under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER", "ROCTX")) for k in os.environ)
-        if world == 1 and not args.no_traffic and not under_profiler:   # (never a profiler inside a profiler)
+        if args.full and world == 1 and not args.no_traffic and not under_profiler:   # (never a profiler inside a profiler)
             eng.close()                                   # (everything the line needs from it has been taken)
             eng = None
             traffic_detail = measure_traffic(args)

@@ -273,7 +273,9 @@ CXX
   cut_lines "$V0" "$V0"
   echo '#line 1 "reference:parse_args.cpp"'
   sed -e '/#include "ngsLD.hpp"/d' "$REF/parse_args.cpp"
+# (the library is found relative to this .so, not by the absolute path of the tree it was built in: oracle/_ref may be built in
+# one checkout and used in another)
 } | g++ -x c++ -O2 -w -fPIC -shared -ffp-contract=off -I"$HERE/../include" -o "$HERE/_ref/libngsld_ref_hip.so" - \
-      -L"$LIBDIR" -lngsld -Wl,-rpath,"$LIBDIR" -Wl,-rpath,/opt/rocm/lib -lz -lpthread
+      -L"$LIBDIR" -lngsld -Wl,-rpath,'$ORIGIN/../../ngsld_amd' -Wl,-rpath,/opt/rocm/lib -lz -lpthread
 echo "built $HERE/_ref/libngsld_ref_hip.so (the reference's main with ngsLD.cpp:153-198 replaced by integration/ngsld_binding.h)"
 

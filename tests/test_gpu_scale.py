@@ -210,8 +210,8 @@ def test_c5_full_size_on_one_gpu_through_the_bench():
     free, total = capi.device_memory(0) if hasattr(capi, "device_memory") else (None, None)
     if free is not None and free < 150 * 2 ** 30:
         pytest.skip(f"{free / 2 ** 30:.0f} GiB of device memory free: the full-size run needs ~135 GiB")
-    cmd = [sys.executable, "bench.py", "--config", "c4", "--steps", "1", "--warmup", "0", "--no-traffic", "--no-e2e", "--no-sink",
-           "--cpu-seconds", "4"]
+    cmd = [sys.executable, "bench.py", "--config", "c4", "--steps", "1", "--warmup", "0", "--full", "--no-traffic", "--no-e2e",
+           "--no-sink", "--cpu-seconds", "4"]
     r = subprocess.run(cmd, cwd=capi.REPO_DIR, capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -55,8 +55,8 @@ def test_cohort_sizes_past_the_old_cliffs_keep_their_rate(n_ind, floor):
 # round, profiles/r06 -- floors 1.35e8 / 1.9e8.)
 @pytest.mark.parametrize("flags,floor", [(["--mono-frac", "0.2"], 1.35e8), (["--sfs"], 1.9e8)])
 def test_uncalled_input_is_replayed_on_the_device(flags, floor):
-    cmd = [sys.executable, "bench.py", "--config", "c2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-sink", "--no-e2e",
-           "--no-traffic"] + flags
+    cmd = [sys.executable, "bench.py", "--config", "c2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-sink",
+           "--no-e2e", "--no-traffic"] + flags
     r = subprocess.run(cmd, cwd=capi.REPO_DIR, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -238,5 +238,9 @@ def run_patched_ref_program(flags: list[str], out_path: str, threads: int = 1, t
     import sys
     e = dict(os.environ)
     e.update(env or {})
+    # the program links THIS checkout's libngsld.so: oracle/_ref may have been built elsewhere and be a link to a directory
+    # outside the tree, where the library's own $ORIGIN-relative run path does not lead here
+    lib_dir = os.path.join(os.path.dirname(HERE), "ngsld_amd")
+    e["LD_LIBRARY_PATH"] = os.pathsep.join([lib_dir] + ([e["LD_LIBRARY_PATH"]] if e.get("LD_LIBRARY_PATH") else []))
     return subprocess.run([sys.executable, "-c", _REF_HIP_CHILD, *flags, "--n_threads", str(threads), "--out", out_path],
                           capture_output=True, text=True, timeout=timeout, env=e)

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r06_small; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python $R/bench.py --sites 10000 --mono-frac 0.2 --steps 5 --warmup 2 --no-cpu --no-sink --no-e2e --no-traffic --no-unfiltered --no-other-configs > $O/run.json 2> $O/run.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python $R/bench.py --sites 10000 --mono-frac 0.2 --steps 5 --warmup 2 --full --no-cpu --no-sink --no-e2e --no-traffic --no-unfiltered --no-other-configs > $O/run.json 2> $O/run.err
 python - <<PY
 import csv,glob,json
 f=glob.glob("$O/trace/**/*kernel_stats.csv",recursive=True)[0]
