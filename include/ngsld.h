@@ -389,6 +389,44 @@ int ngsld_multi_last_distribution(void);
  * reason in err. */
 int ngsld_rccl_selftest(int device, uint64_t bytes, char *err, size_t errlen);
 
+/* ---- LD pruning on the device (PRUNE.md) ------------------------------------------------------------------------------
+ * The sites the reference's scripts/prune_graph.pl keeps (its prune_graph_idx path) for the TSV this context's plan would
+ * print -- without the TSV: the pairs run again chunk by chunk into device records (every pair kernel, the exact-order replay
+ * included), the edges are taken from them on the device, the graph is built and pruned there, a small remainder on the host.
+ * A site is a node iff it is one end of a planned pair (and in the subset, when one is given); edge weights are the chosen
+ * field as printed ("%f" read back), the rule and its deviations are in PRUNE.md.  Both structs start with struct_size: set it
+ * to sizeof(the struct) of your header (params: must equal this library's; stats: up to that many bytes are written). */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_prune_params) */
+  int32_t field;              /* TSV column of the weight: 4 r2_ExpG, 5 D, 6 D', 7 r2 (the script's --field_weight, default 7) */
+  double max_kb_dist;         /* an edge needs dist <= max_kb_dist * 1000 (INFINITY: no limit) */
+  double min_weight;          /* an edge needs weight >= min_weight (default 0) */
+  int32_t weight_type;        /* 'a' |weight| (default), 'e' weight as it is, 'n' every edge counts 1 */
+  int32_t keep_heavy;         /* != 0: the heaviest node stays and its neighbours go */
+  int32_t precision;          /* edge label = trunc(weight * 10^precision), 0..15 (default 4) */
+  int32_t reserved;           /* 0 */
+  const char *const *subset;  /* NULL: every site; else n_subset labels -- only those sites are nodes */
+  uint64_t n_subset;
+} ngsld_prune_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_prune_stats) */
+  uint32_t reserved;
+  uint64_t pairs;             /* pairs computed */
+  uint64_t nodes, edges;      /* of the graph */
+  uint64_t kept, excluded;    /* nodes == kept + excluded */
+  uint64_t rounds;            /* parallel rounds on the device */
+  uint64_t host_nodes, host_edges, host_steps;  /* the remainder finished on the host, and its heaviest-node steps */
+  double pairs_ms, edges_ms, graph_ms, rounds_ms, host_ms, total_ms;  /* phases: pair kernels + replay, edge extraction
+                                                 (kernel time), CSR build, device rounds, host finish, the whole call */
+} ngsld_prune_stats;
+
+/* Prune after ngsld_plan.  labels = n_sites C strings, the TSV's first two columns (NULL: every label is "(null)").
+ * site_state[n_sites] receives 0 (not a node), 1 (kept) or 2 (excluded).  stats may be NULL.  Two node sites with the same
+ * label: NGSLD_ERR_INVALID naming it; an edge label of 2^62 or more: NGSLD_ERR_UNSUPPORTED naming the pair. */
+int ngsld_prune(ngsld_ctx *ctx, const ngsld_prune_params *params, const char *const *labels, uint8_t *site_state,
+                ngsld_prune_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

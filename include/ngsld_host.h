@@ -101,6 +101,19 @@ int ngsld_host_gz_close(ngsld_gz *gz);
 int ngsld_host_replay_pair(const double *raw1, const double *raw2, uint64_t n_ind, const ngsld_geno_opts *opts,
                            ngsld_rec_std *std_rec, ngsld_rec_ext *ext_rec, double *maf_out);
 
+/* LD pruning on the host (PRUNE.md), the exact sequential rule of prune_graph.pl's prune_graph_idx on an edge list: nodes
+ * 0 .. n_nodes-1, edges (a[e], b[e]) with integer labels of any sign (at most one edge per pair of nodes).  Until the heaviest
+ * node -- largest sum of its live edges' labels, ties to the lower rank[] (NULL: the node index) -- weighs <= 0: remove it
+ * (keep_heavy == 0) or remove all its live neighbours (keep_heavy != 0).  excluded[n_nodes] receives 1 for a removed node;
+ * n_steps (may be NULL) the number of heaviest-node steps.  NGSLD_ERR_INVALID for a bad edge, NGSLD_ERR_UNSUPPORTED when a
+ * node's labels cannot be summed exactly in 64 bits. */
+int ngsld_host_prune_graph(uint64_t n_nodes, const uint64_t *rank, uint64_t n_edges, const uint32_t *a, const uint32_t *b,
+                           const int64_t *label, int keep_heavy, uint8_t *excluded, uint64_t *n_steps);
+/* The edge label of one value x with the device's own code (ld_prune.h): x as "%f" prints it and a reader reads it back,
+ * |.| for type 'a', 1 for 'n', times 10^prec (0..15), truncated.  NGSLD_ERR_INVALID for NaN / inf (never an edge) or bad
+ * arguments, NGSLD_ERR_UNSUPPORTED when |label| would reach 2^62. */
+int ngsld_host_prune_label(double x, int prec, char type, int64_t *label);
+
 #ifdef __cplusplus
 }
 #endif

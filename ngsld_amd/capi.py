@@ -92,6 +92,7 @@ SYMBOLS = [
     "ngsld_host_geno_size_ok", "ngsld_host_read_geno_bin", "ngsld_host_read_geno_text", "ngsld_host_format_header", "ngsld_host_format_pair",
     "ngsld_host_format_double", "ngsld_host_write_batch", "ngsld_host_replay_pair", "ngsld_host_missing_call_log",
     "ngsld_host_gz_open", "ngsld_host_gz_close",
+    "ngsld_prune", "ngsld_host_prune_graph", "ngsld_host_prune_label",
 ]
 
 
@@ -100,6 +101,22 @@ class ReplayStats(C.Structure):
     _fields_ = [("pairs_flagged", C.c_uint64), ("pairs_replayed", C.c_uint64), ("pairs_on_device", C.c_uint64),
                 ("pairs_on_host", C.c_uint64), ("sites_reevaluated", C.c_uint64), ("exact_store", C.c_int32),
                 ("text_rows_patched", C.c_int32), ("exact_store_build_s", C.c_double), ("sites_degenerate", C.c_uint64)]
+
+
+class PruneParams(C.Structure):
+    """ngsld_prune_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("max_kb_dist", C.c_double), ("min_weight", C.c_double),
+                ("weight_type", C.c_int32), ("keep_heavy", C.c_int32), ("precision", C.c_int32), ("reserved", C.c_int32),
+                ("subset", C.POINTER(C.c_char_p)), ("n_subset", C.c_uint64)]
+
+
+class PruneStats(C.Structure):
+    """ngsld_prune_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("nodes", C.c_uint64),
+                ("edges", C.c_uint64), ("kept", C.c_uint64), ("excluded", C.c_uint64), ("rounds", C.c_uint64),
+                ("host_nodes", C.c_uint64), ("host_edges", C.c_uint64), ("host_steps", C.c_uint64),
+                ("pairs_ms", C.c_double), ("edges_ms", C.c_double), ("graph_ms", C.c_double), ("rounds_ms", C.c_double),
+                ("host_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class NgsldError(RuntimeError):
@@ -207,8 +224,38 @@ def lib() -> C.CDLL:
         if hasattr(L, "ngsld_host_gz_open"):
             L.ngsld_host_gz_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(C.c_int)]
             L.ngsld_host_gz_close.argtypes = [vp]
+        if hasattr(L, "ngsld_prune"):
+            L.ngsld_prune.argtypes = [vp, C.POINTER(PruneParams), C.POINTER(C.c_char_p), vp, C.POINTER(PruneStats)]
+            L.ngsld_host_prune_graph.argtypes = [u64, vp, u64, vp, vp, vp, C.c_int, vp, C.POINTER(u64)]
+            L.ngsld_host_prune_label.argtypes = [dbl, C.c_int, C.c_char, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
+
+
+def prune_label(x: float, prec: int = 4, weight_type: str = "a") -> int | None:
+    """ngsld_host_prune_label: the edge label of one value as the pruner sees it printed; None for NaN / inf."""
+    out = C.c_int64()
+    rc = lib().ngsld_host_prune_label(float(x), prec, weight_type.encode(), C.byref(out))
+    if rc == ERR_INVALID:
+        return None
+    if rc != OK:
+        raise NgsldError(rc, "label out of range")
+    return out.value
+
+
+def prune_graph(n_nodes: int, a, b, label, keep_heavy: bool = False, rank=None) -> tuple[np.ndarray, int]:
+    """ngsld_host_prune_graph: the exact sequential pruner on an edge list; returns (excluded[n_nodes] bool, steps)."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    lab = np.ascontiguousarray(label, dtype=np.int64)
+    rk = None if rank is None else np.ascontiguousarray(rank, dtype=np.uint64)
+    excl = np.zeros(max(n_nodes, 1), dtype=np.uint8)
+    steps = C.c_uint64()
+    rc = lib().ngsld_host_prune_graph(n_nodes, None if rk is None else rk.ctypes.data, len(a), a.ctypes.data, b.ctypes.data,
+                                      lab.ctypes.data, int(keep_heavy), excl.ctypes.data, C.byref(steps))
+    if rc != OK:
+        raise NgsldError(rc, "ngsld_host_prune_graph failed")
+    return excl[:n_nodes].astype(bool), steps.value
 
 
 # ------------------------------------------------------------------------------------------------
@@ -835,3 +882,18 @@ class Engine:
         ms, nl, npairs = C.c_double(), C.c_uint64(), C.c_uint64()
         self._check(self._L.ngsld_last_kernel_time(self._h, C.byref(ms), C.byref(nl), C.byref(npairs)))
         return ms.value, nl.value, npairs.value
+
+    def prune(self, labels: list[str] | None, field: int = 7, max_kb_dist: float = float("inf"), min_weight: float = 0.0,
+              weight_type: str = "a", keep_heavy: bool = False, subset: list[str] | None = None,
+              precision: int = 4) -> tuple[np.ndarray, dict]:
+        """LD pruning of the planned pairs on the device (ngsld_prune): (site_state, stats) -- site_state[s] is 0 (not a node),
+        1 (kept) or 2 (excluded); labels None = every label "(null)"."""
+        arr = None if labels is None else (C.c_char_p * len(labels))(*[l.encode() for l in labels])
+        sub = None if subset is None else (C.c_char_p * max(len(subset), 1))(*[l.encode() for l in subset])
+        p = PruneParams(C.sizeof(PruneParams), field, float(max_kb_dist), float(min_weight), ord(weight_type), int(keep_heavy),
+                        precision, 0, sub, 0 if subset is None else len(subset))
+        st = PruneStats()
+        st.struct_size = C.sizeof(PruneStats)
+        state = np.zeros(max(self.n_sites, 1), dtype=np.uint8)
+        self._check(self._L.ngsld_prune(self._h, C.byref(p), arr, state.ctypes.data, C.byref(st)))
+        return state[:self.n_sites], {k: getattr(st, k) for k, _ in PruneStats._fields_ if k not in ("struct_size", "reserved")}

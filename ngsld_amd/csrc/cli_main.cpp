@@ -8,7 +8,11 @@
 //     caps the device memory: a windowed run on binary input that does not fit is streamed slab by slab;
 //   * --devices 0-7 (or 0,2,5; new) runs the job on several GPUs of the node from this one process (ngsld_run_multi):
 //     the rows are cut into one part per device, the output is the single-device output;
+//   * --prune_out FILE (new) and the other --prune_* flags: the sites scripts/prune_graph.pl would keep, pruned on the device
+//     (ngsld_prune, PRUNE.md); without --out no TSV is written.  Exact flag names only: they are taken out of argv before
+//     getopt runs, so the reference's flags keep every abbreviation and message they have;
 #include <getopt.h>
+#include <zlib.h>
 #include <sys/stat.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -92,6 +96,169 @@ const char *pos_error_function(const char *msg, const char *path) {
   if (std::strcmp(msg, "cannot open file!") == 0) return path != nullptr && access(path, R_OK) == 0 ? "read_split" : "read_file";
   if (std::strcmp(msg, "invalid number of fields in file!") == 0) return "read_split";
   return "read_dist";
+}
+
+// ---- --prune_* (new): LD pruning on the device ----
+struct PruneArgs {
+  bool given = false;  // any --prune_* flag
+  const char *out = nullptr, *excl = nullptr, *subset_file = nullptr;
+  const char *field = nullptr, *type = nullptr, *precision = nullptr, *max_kb_dist = nullptr, *min_weight = nullptr;
+  bool keep_heavy = false;
+  ngsld_prune_params p{};
+  std::vector<std::string> subset;
+};
+
+// Takes the --prune_* flags (one or two dashes, "--name value" or "--name=value") out of argv; the values are checked by
+// check_prune_args once the reference's own arguments have been.
+void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
+  static const char *const kValued[] = {"prune_out", "prune_excl", "prune_subset", "prune_field", "prune_weight_type",
+                                        "prune_precision", "prune_max_kb_dist", "prune_min_weight"};
+  const char **dst[] = {&pa->out, &pa->excl, &pa->subset_file, &pa->field, &pa->type, &pa->precision, &pa->max_kb_dist,
+                        &pa->min_weight};
+  int w = 1;
+  for (int i = 1; i < *argc; ++i) {
+    const char *a = argv[i];
+    if (std::strcmp(a, "--") == 0) {  // (getopt's end of options: the rest is not ours)
+      while (i < *argc) argv[w++] = argv[i++];
+      break;
+    }
+    const char *name = a[0] == '-' ? (a[1] == '-' ? a + 2 : a + 1) : nullptr;
+    if (name == nullptr || std::strncmp(name, "prune_", 6) != 0) {
+      argv[w++] = argv[i];
+      continue;
+    }
+    const char *eq = std::strchr(name, '=');
+    const std::string key = eq ? std::string(name, eq) : std::string(name);
+    pa->given = true;
+    if (key == "prune_keep_heavy" && eq == nullptr) {
+      pa->keep_heavy = true;
+      continue;
+    }
+    bool known = false;
+    for (size_t k = 0; k < sizeof(kValued) / sizeof(kValued[0]); ++k) {
+      if (key != kValued[k]) continue;
+      known = true;
+      if (eq != nullptr) {
+        *dst[k] = eq + 1;
+      } else if (i + 1 < *argc) {
+        *dst[k] = argv[++i];
+      } else {
+        const std::string msg = "--" + key + " needs a value!";
+        error(__FUNCTION__, msg.c_str());
+      }
+    }
+    if (!known) {
+      const std::string msg = "unknown option --" + key + "!";
+      error(__FUNCTION__, msg.c_str());
+    }
+  }
+  argv[w] = nullptr;
+  *argc = w;
+}
+
+bool parse_double(const char *txt, double *out) {
+  char *end = nullptr;
+  if (txt == nullptr || *txt == 0) return false;
+  *out = strtod(txt, &end);
+  return *end == 0 && !std::isnan(*out);
+}
+
+void check_prune_args(const Params &pars, PruneArgs *pa) {
+  if (!pa->given) return;
+  if (pa->out == nullptr || *pa->out == 0) error(__FUNCTION__, "the --prune_* options need --prune_out FILE!");
+  ngsld_prune_params &p = pa->p;
+  p.struct_size = sizeof(p);
+  p.field = 7;
+  p.max_kb_dist = INFINITY;
+  p.min_weight = 0;
+  p.weight_type = 'a';
+  p.precision = 4;
+  p.keep_heavy = pa->keep_heavy ? 1 : 0;
+  if (pa->field) {
+    char *end = nullptr;
+    const long f = strtol(pa->field, &end, 10);
+    if (*pa->field == 0 || *end != 0 || f < 4 || f > 7)
+      error(__FUNCTION__, "--prune_field must be 4 (r2_ExpG), 5 (D), 6 (D') or 7 (r2)!");
+    p.field = (int32_t)f;
+  }
+  if (pa->type) {
+    if (std::strlen(pa->type) != 1 || std::strchr("aen", pa->type[0]) == nullptr)
+      error(__FUNCTION__, "--prune_weight_type must be a, e or n!");
+    p.weight_type = pa->type[0];
+  }
+  if (pa->precision) {
+    char *end = nullptr;
+    const long v = strtol(pa->precision, &end, 10);
+    if (*pa->precision == 0 || *end != 0 || v < 0 || v > 15) error(__FUNCTION__, "--prune_precision must be an integer in [0,15]!");
+    p.precision = (int32_t)v;
+  }
+  if (pa->max_kb_dist && (!parse_double(pa->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
+    error(__FUNCTION__, "--prune_max_kb_dist must be a number >= 0 (or inf)!");
+  if (pa->min_weight && !parse_double(pa->min_weight, &p.min_weight)) error(__FUNCTION__, "--prune_min_weight must be a number!");
+  if (pa->excl != nullptr && *pa->excl == 0) error(__FUNCTION__, "--prune_excl needs a file name!");
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--prune_out runs on one device: it cannot be combined with --devices!");
+  if (pa->subset_file) {  // one label per line, plain or gzip-compressed (the script's IO::Zlib reads both)
+    gzFile f = gzopen(pa->subset_file, "rb");
+    if (f == nullptr) error(__FUNCTION__, "cannot open --prune_subset file!");
+    std::string line;
+    char buf[4096];
+    while (gzgets(f, buf, sizeof(buf)) != nullptr) {
+      line += buf;
+      if (!line.empty() && line.back() == '\n') {
+        line.pop_back();
+        pa->subset.push_back(line);
+        line.clear();
+      }
+    }
+    if (!line.empty()) pa->subset.push_back(line);
+    gzclose(f);
+  }
+}
+
+// labels one per line, in site order; a name ending in .gz is written gzip-compressed
+void write_labels(const char *path, const std::vector<const char *> &labels) {
+  const size_t n = std::strlen(path);
+  if (n > 3 && std::strcmp(path + n - 3, ".gz") == 0) {
+    gzFile f = gzopen(path, "wb6");
+    if (f == nullptr) error(__FUNCTION__, "cannot open pruning output file!");
+    for (const char *l : labels)
+      if (gzputs(f, l) < 0 || gzputc(f, '\n') < 0) error(__FUNCTION__, "cannot write pruning output file!");
+    if (gzclose(f) != Z_OK) error(__FUNCTION__, "cannot write pruning output file!");
+    return;
+  }
+  FILE *f = fopen(path, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open pruning output file!");
+  for (const char *l : labels) fprintf(f, "%s\n", l);
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write pruning output file!");
+}
+
+void run_prune(ngsld_ctx *ctx, const Params &pars, PruneArgs &pa, const ngsld_pos *pos) {
+  std::vector<const char *> lab(pars.n_sites, "(null)");
+  if (pos)
+    for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  std::vector<const char *> sub;
+  for (const std::string &x : pa.subset) sub.push_back(x.c_str());
+  if (pa.subset_file) {
+    pa.p.subset = sub.data();
+    pa.p.n_subset = sub.size();
+  }
+  static const char *const kEmpty[1] = {""};
+  if (pa.subset_file && sub.empty()) pa.p.subset = kEmpty;  // (an empty subset: no site is a node)
+  std::vector<uint8_t> state(pars.n_sites);
+  ngsld_prune_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_prune(ctx, &pa.p, lab.data(), state.data(), &st) != NGSLD_OK) error("ngsld_prune", ngsld_last_error(ctx));
+  std::vector<const char *> kept, excl;
+  for (uint64_t s = 0; s < pars.n_sites; s++) {
+    if (state[s] == 1) kept.push_back(lab[s]);
+    if (state[s] == 2) excl.push_back(lab[s]);
+  }
+  write_labels(pa.out, kept);
+  if (pa.excl) write_labels(pa.excl, excl);
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> Pruning: %lu nodes, %lu edges: %lu kept, %lu excluded (%lu rounds on the device, %lu nodes finished on the host)\n",
+            (unsigned long)st.nodes, (unsigned long)st.edges, (unsigned long)st.kept, (unsigned long)st.excluded,
+            (unsigned long)st.rounds, (unsigned long)st.host_nodes);
 }
 
 void parse_cmd_args(Params *pars, int argc, char **argv) {
@@ -506,7 +673,11 @@ int main(int argc, char **argv) {
   // mapping became fork-proof); this process is short-lived, single-purpose and never forks.  NGSLD_PIN_REGISTER=0 turns it off.
   setenv("NGSLD_PIN_REGISTER", "1", /*overwrite=*/0);
   Params pars;
+  PruneArgs prune;
+  take_prune_args(&argc, argv, &prune);
   parse_cmd_args(&pars, argc, argv);
+  check_prune_args(pars, &prune);
+  const bool write_tsv = !prune.given || pars.out != NULL;  // --prune_out without --out: no TSV
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -536,10 +707,12 @@ int main(int argc, char **argv) {
     pars.out_fh = fopen(pars.out, "w");
   }
   if (pars.out_fh == NULL) error(__FUNCTION__, "cannot open output file!");
-  char hdr[512];
-  const size_t hn = ngsld_host_format_header(hdr, sizeof(hdr), pars.extend_out);
-  fwrite(hdr, 1, hn, pars.out_fh);
-  fflush(pars.out_fh);
+  if (write_tsv) {
+    char hdr[512];
+    const size_t hn = ngsld_host_format_header(hdr, sizeof(hdr), pars.extend_out);
+    fwrite(hdr, 1, hn, pars.out_fh);
+    fflush(pars.out_fh);
+  }
 
   ngsld_host_set_threads((int)pars.n_threads);
   timing_report.mark("arguments, output header");
@@ -641,6 +814,8 @@ int main(int argc, char **argv) {
     // From 4 GiB: a 1.2 GB file ran 0.5 s faster resident (2.2 s) than in slabs, a 5.8 GB one 0.5 s slower.
     slab_sites = std::min<uint64_t>(ngsld_sites_for_budget(pars.n_ind, budget, copies), (pars.n_sites + 5) / 6);
   }
+  if (slab_sites > 0 && prune.given)
+    error(__FUNCTION__, "--prune_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -657,7 +832,7 @@ int main(int argc, char **argv) {
   // and prepped (pinning ~0.7 GB costs ~0.1 s, which the first batches of the run used to wait for).  Only now that the run is
   // known to be resident: a streamed run uses contexts of its own, and destroying this one had to wait for the pinning to
   // finish only to undo it
-  if (!host_text_only())
+  if (write_tsv && !host_text_only())
     (void)ngsld_reserve_text_buffers(ctx, pars.extend_out ? 190 : 95);
 
   // ---- read input data (ngsLD.cpp:85-114; the arithmetic runs on the device) ----
@@ -759,7 +934,7 @@ int main(int argc, char **argv) {
   // The rows are formatted on the device (the fprintf block of calc_pair_LD, ngsLD.cpp:310-352, at kernel rates); a
   // batch the device formatter cannot take arrives as records and goes through the --n_threads host formatter as
   // before.  NGSLD_HOST_TEXT=1 keeps everything on the host formatter (A/B, tests).
-  if (!host_text_only()) {
+  if (write_tsv && !host_text_only()) {
     std::vector<const char *> lab;
     if (pos) {
       lab.resize(pars.n_sites);
@@ -775,11 +950,15 @@ int main(int argc, char **argv) {
   sink.pos_dist = pos ? ngsld_host_pos_dist(pos) : nullptr;
   sink.maf = &maf;
   timing_report.mark("labels to the device");
-  rc = ngsld_run(ctx, 0, pars.n_sites, write_batch, &sink);
+  rc = write_tsv ? ngsld_run(ctx, 0, pars.n_sites, write_batch, &sink) : NGSLD_OK;
   timing_report.mark("pair kernels + text + write");
   if (rc == NGSLD_ERR_MAF_RANGE) error("haplo_freq", ngsld_last_error(ctx));
   if (rc != NGSLD_OK) error("ngsld_run", ngsld_last_error(ctx));
-  if (pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
+  if (prune.given) {  // (a second pass of the pair kernels when the TSV was written too)
+    run_prune(ctx, pars, prune, pos);
+    timing_report.mark("pruning");
+  }
+  if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)
     ngsld_replay_stats_t st{};
     (void)ngsld_replay_info(ctx, &st);
