@@ -427,6 +427,41 @@ typedef struct {
 int ngsld_prune(ngsld_ctx *ctx, const ngsld_prune_params *params, const char *const *labels, uint8_t *site_state,
                 ngsld_prune_stats *stats);
 
+/* ---- LD decay on the device (DECAY.md) -----------------------------------------------------------------------------------
+ * The bins the reference's scripts/fit_LDdecay.R averages (its default mean, --fit_bin_size > 1) for the TSV this context's
+ * plan would print -- without the TSV: the pairs run again chunk by chunk into device records (every pair kernel, the
+ * exact-order replay included) and a kernel bins them.  A row counts iff both printed maf >= min_maf, dist (as printed) is finite
+ * and < max_kb_dist * 1000, and every chosen field is finite; it goes to the right-closed bin (k*B, (k+1)*B], reported at k*B.
+ * A bin's mean is the double nearest to the exact mean of the printed ("%f") values: the sums are exact integers.  The rule
+ * and its deviations are in DECAY.md.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_decay_params) */
+  uint32_t fields;            /* mask of the TSV columns binned: 1 r2_ExpG, 2 D, 4 D' (the script's Dp), 8 r2 (its default) */
+  double bin_size;            /* B > 1 (the script's --fit_bin_size, default 250) */
+  double max_kb_dist;         /* a row needs dist < max_kb_dist * 1000 (INFINITY: no limit, the script's default) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+} ngsld_decay_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_decay_stats) */
+  uint32_t lds;               /* 1: the bins were accumulated per workgroup in LDS, 0: in global memory */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows in some bin */
+  uint64_t bins;              /* non-empty bins (what ngsld_decay_bins returns) */
+  uint64_t bin_slots;         /* bins sized from the plan */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, bin_ms, total_ms;  /* pair kernels + replay, the bin kernel (kernel time), the whole call */
+} ngsld_decay_stats;
+
+/* Bin after ngsld_plan; the context keeps the bins until the next ngsld_decay.  stats may be NULL.  NGSLD_ERR_UNSUPPORTED for a
+ * value of 2^38 micro-units or more (|x| >= 274877.906944, naming the pair), a finite max_kb_dist with non-integer position
+ * gaps, or more than 2^22 bins. */
+int ngsld_decay(ngsld_ctx *ctx, const ngsld_decay_params *params, ngsld_decay_stats *stats);
+/* The last ngsld_decay's non-empty bins in increasing distance: up to cap of them into dist[] (the bin's lower break),
+ * count[] (rows) and mean[] (one value per chosen field, in TSV column order: mean[i * n_fields + f]).  Any pointer may be
+ * NULL; *n_bins (may be NULL) receives the number of bins. */
+int ngsld_decay_bins(ngsld_ctx *ctx, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,21 @@ int ngsld_host_prune_graph(uint64_t n_nodes, const uint64_t *rank, uint64_t n_ed
  * arguments, NGSLD_ERR_UNSUPPORTED when |label| would reach 2^62. */
 int ngsld_host_prune_label(double x, int prec, char type, int64_t *label);
 
+/* The LD decay fit of scripts/fit_LDdecay.R (DECAY.md) on n_bins bin means value[] at distances dist[], field 4 (r2_ExpG),
+ * 6 (D') or 7 (r2).  r2 / r2_ExpG with n_ind == 0: (h - l) / (1 + C d) + l, C in [0, 1], 0 <= l <= h <= 1; with n_ind > 0 the
+ * one-parameter Hill-Weir curve in C d (h = l = 0 reported); D': l + (h - l) (1 - d rr / 10^6)^t, t >= 0, 0 <= l <= h <= 1,
+ * rr = recomb_rate.  Returns the global minimum of the script's sum of squares over that region, found deterministically: the
+ * exact 2-variable QP in (h, l) for each rate, the rate from a log grid and golden-section refinement.  NGSLD_ERR_INVALID for
+ * D (5), D' with n_ind > 0, no bins, a non-finite input, a D' bin with d rr / 10^6 > 1, or bad arguments. */
+typedef struct {
+  double rate;                /* C (r2, r2_ExpG) or t (D') */
+  double ld_max, ld_min;      /* h, l */
+  double sse;                 /* the script's sum of squares at the result */
+  uint64_t n_bins;
+} ngsld_decay_fit_result;
+int ngsld_host_decay_fit(uint64_t n_bins, const double *dist, const double *value, int field, double n_ind, double recomb_rate,
+                         ngsld_decay_fit_result *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,7 @@ SYMBOLS = [
     "ngsld_host_format_double", "ngsld_host_write_batch", "ngsld_host_replay_pair", "ngsld_host_missing_call_log",
     "ngsld_host_gz_open", "ngsld_host_gz_close",
     "ngsld_prune", "ngsld_host_prune_graph", "ngsld_host_prune_label",
+    "ngsld_decay", "ngsld_decay_bins", "ngsld_host_decay_fit",
 ]
 
 
@@ -117,6 +118,29 @@ class PruneStats(C.Structure):
                 ("host_nodes", C.c_uint64), ("host_edges", C.c_uint64), ("host_steps", C.c_uint64),
                 ("pairs_ms", C.c_double), ("edges_ms", C.c_double), ("graph_ms", C.c_double), ("rounds_ms", C.c_double),
                 ("host_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class DecayParams(C.Structure):
+    """ngsld_decay_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("bin_size", C.c_double), ("max_kb_dist", C.c_double),
+                ("min_maf", C.c_double)]
+
+
+class DecayStats(C.Structure):
+    """ngsld_decay_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("bins", C.c_uint64), ("bin_slots", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double),
+                ("bin_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class DecayFitResult(C.Structure):
+    """ngsld_decay_fit_result (include/ngsld_host.h)."""
+    _fields_ = [("rate", C.c_double), ("ld_max", C.c_double), ("ld_min", C.c_double), ("sse", C.c_double),
+                ("n_bins", C.c_uint64)]
+
+
+# the statistics LD decay bins, in TSV column order (bit k of ngsld_decay_params.fields = column 4 + k)
+DECAY_FIELDS = ("r2_ExpG", "D", "Dp", "r2")
 
 
 class NgsldError(RuntimeError):
@@ -228,6 +252,10 @@ def lib() -> C.CDLL:
             L.ngsld_prune.argtypes = [vp, C.POINTER(PruneParams), C.POINTER(C.c_char_p), vp, C.POINTER(PruneStats)]
             L.ngsld_host_prune_graph.argtypes = [u64, vp, u64, vp, vp, vp, C.c_int, vp, C.POINTER(u64)]
             L.ngsld_host_prune_label.argtypes = [dbl, C.c_int, C.c_char, C.POINTER(C.c_int64)]
+        if hasattr(L, "ngsld_decay"):
+            L.ngsld_decay.argtypes = [vp, C.POINTER(DecayParams), C.POINTER(DecayStats)]
+            L.ngsld_decay_bins.argtypes = [vp, u64, vp, vp, vp, C.POINTER(u64)]
+            L.ngsld_host_decay_fit.argtypes = [u64, vp, vp, C.c_int, dbl, dbl, C.POINTER(DecayFitResult)]
         _lib = L
     return _lib
 
@@ -241,6 +269,23 @@ def prune_label(x: float, prec: int = 4, weight_type: str = "a") -> int | None:
     if rc != OK:
         raise NgsldError(rc, "label out of range")
     return out.value
+
+
+def decay_fit(dist, values, field: str = "r2", n_ind: float = 0, recomb_rate: float = 1.0) -> dict:
+    """ngsld_host_decay_fit: the LD decay fit of fit_LDdecay.R on bin means (DECAY.md); field r2, r2_ExpG or Dp.  Returns
+    {rate, ld_max, ld_min, sse, n_bins}; NgsldError for D, Dp with n_ind > 0, no bins or a bad value."""
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if d.shape != v.shape or d.ndim != 1:
+        raise ValueError("dist and values must be 1-D arrays of one length")
+    if field not in DECAY_FIELDS:
+        raise ValueError(f"field must be one of {DECAY_FIELDS}")
+    out = DecayFitResult()
+    rc = lib().ngsld_host_decay_fit(len(d), d.ctypes.data, v.ctypes.data, 4 + DECAY_FIELDS.index(field), float(n_ind),
+                                    float(recomb_rate), C.byref(out))
+    if rc != OK:
+        raise NgsldError(rc, f"ngsld_host_decay_fit refused the {field} fit")
+    return {k: getattr(out, k) for k, _ in DecayFitResult._fields_}
 
 
 def prune_graph(n_nodes: int, a, b, label, keep_heavy: bool = False, rank=None) -> tuple[np.ndarray, int]:
@@ -897,3 +942,29 @@ class Engine:
         state = np.zeros(max(self.n_sites, 1), dtype=np.uint8)
         self._check(self._L.ngsld_prune(self._h, C.byref(p), arr, state.ctypes.data, C.byref(st)))
         return state[:self.n_sites], {k: getattr(st, k) for k, _ in PruneStats._fields_ if k not in ("struct_size", "reserved")}
+
+    def decay(self, ld=("r2",), bin_size: float = 250, max_kb_dist: float = float("inf"),
+              min_maf: float = 0.0) -> tuple[dict, dict]:
+        """LD decay bins of the planned pairs on the device (ngsld_decay): (bins, stats).  bins holds numpy arrays "dist" (each
+        non-empty bin's lower break), "n" (rows) and one mean per statistic of ld (r2_ExpG, D, Dp, r2)."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        names = [f for k, f in enumerate(DECAY_FIELDS) if (mask >> k) & 1]
+        p = DecayParams(C.sizeof(DecayParams), mask, float(bin_size), float(max_kb_dist), float(min_maf))
+        st = DecayStats()
+        st.struct_size = C.sizeof(DecayStats)
+        self._check(self._L.ngsld_decay(self._h, C.byref(p), C.byref(st)))
+        nb = st.bins
+        dist = np.zeros(max(nb, 1))
+        cnt = np.zeros(max(nb, 1), dtype=np.uint64)
+        mean = np.zeros((max(nb, 1), len(names)))
+        got = C.c_uint64()
+        self._check(self._L.ngsld_decay_bins(self._h, nb, dist.ctypes.data, cnt.ctypes.data, mean.ctypes.data, C.byref(got)))
+        assert got.value == nb
+        bins = {"dist": dist[:nb], "n": cnt[:nb]}
+        for k, f in enumerate(names):
+            bins[f] = mean[:nb, k].copy()
+        return bins, {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}

@@ -11,6 +11,8 @@
 //   * --prune_out FILE (new) and the other --prune_* flags: the sites scripts/prune_graph.pl would keep, pruned on the device
 //     (ngsld_prune, PRUNE.md); without --out no TSV is written.  Exact flag names only: they are taken out of argv before
 //     getopt runs, so the reference's flags keep every abbreviation and message they have;
+//   * --decay_out FILE / --decay_fit FILE (new) and the other --decay_* flags: the distance bins and the decay fit of
+//     scripts/fit_LDdecay.R, binned on the device (ngsld_decay, DECAY.md); taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -108,13 +110,12 @@ struct PruneArgs {
   std::vector<std::string> subset;
 };
 
-// Takes the --prune_* flags (one or two dashes, "--name value" or "--name=value") out of argv; the values are checked by
-// check_prune_args once the reference's own arguments have been.
-void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
-  static const char *const kValued[] = {"prune_out", "prune_excl", "prune_subset", "prune_field", "prune_weight_type",
-                                        "prune_precision", "prune_max_kb_dist", "prune_min_weight"};
-  const char **dst[] = {&pa->out, &pa->excl, &pa->subset_file, &pa->field, &pa->type, &pa->precision, &pa->max_kb_dist,
-                        &pa->min_weight};
+// Takes the flags named prefix* (one or two dashes, "--name value" or "--name=value") out of argv: valued[k]'s value goes to
+// *dst[k], switch_name (may be null) is a flag without a value.  *given: any such flag.  The values are checked once the
+// reference's own arguments have been.
+void take_flags(int *argc, char **argv, const char *prefix, const char *const *valued, const char **const *dst, size_t n_valued,
+                const char *switch_name, bool *switch_on, bool *given) {
+  const size_t plen = std::strlen(prefix);
   int w = 1;
   for (int i = 1; i < *argc; ++i) {
     const char *a = argv[i];
@@ -123,20 +124,20 @@ void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
       break;
     }
     const char *name = a[0] == '-' ? (a[1] == '-' ? a + 2 : a + 1) : nullptr;
-    if (name == nullptr || std::strncmp(name, "prune_", 6) != 0) {
+    if (name == nullptr || std::strncmp(name, prefix, plen) != 0) {
       argv[w++] = argv[i];
       continue;
     }
     const char *eq = std::strchr(name, '=');
     const std::string key = eq ? std::string(name, eq) : std::string(name);
-    pa->given = true;
-    if (key == "prune_keep_heavy" && eq == nullptr) {
-      pa->keep_heavy = true;
+    *given = true;
+    if (switch_name != nullptr && key == switch_name && eq == nullptr) {
+      *switch_on = true;
       continue;
     }
     bool known = false;
-    for (size_t k = 0; k < sizeof(kValued) / sizeof(kValued[0]); ++k) {
-      if (key != kValued[k]) continue;
+    for (size_t k = 0; k < n_valued; ++k) {
+      if (key != valued[k]) continue;
       known = true;
       if (eq != nullptr) {
         *dst[k] = eq + 1;
@@ -154,6 +155,33 @@ void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
   }
   argv[w] = nullptr;
   *argc = w;
+}
+
+// The --prune_* flags out of argv; check_prune_args checks them.
+void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
+  static const char *const kValued[] = {"prune_out", "prune_excl", "prune_subset", "prune_field", "prune_weight_type",
+                                        "prune_precision", "prune_max_kb_dist", "prune_min_weight"};
+  const char **const dst[] = {&pa->out, &pa->excl, &pa->subset_file, &pa->field, &pa->type, &pa->precision, &pa->max_kb_dist,
+                              &pa->min_weight};
+  take_flags(argc, argv, "prune_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "prune_keep_heavy", &pa->keep_heavy,
+             &pa->given);
+}
+
+// ---- --decay_* (new): LD decay bins and fit on the device ----
+struct DecayArgs {
+  bool given = false;  // any --decay_* flag
+  const char *out = nullptr, *fit = nullptr, *ld = nullptr, *bin_size = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr;
+  const char *n_ind = nullptr, *recomb_rate = nullptr;
+  ngsld_decay_params p{};
+  double n_ind_v = 0, recomb_rate_v = 1;
+};
+
+void take_decay_args(int *argc, char **argv, DecayArgs *da) {
+  static const char *const kValued[] = {"decay_out", "decay_fit", "decay_ld", "decay_bin_size", "decay_max_kb_dist",
+                                        "decay_min_maf", "decay_n_ind", "decay_recomb_rate"};
+  const char **const dst[] = {&da->out, &da->fit, &da->ld, &da->bin_size, &da->max_kb_dist, &da->min_maf, &da->n_ind,
+                              &da->recomb_rate};
+  take_flags(argc, argv, "decay_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &da->given);
 }
 
 bool parse_double(const char *txt, double *out) {
@@ -213,6 +241,111 @@ void check_prune_args(const Params &pars, PruneArgs *pa) {
     if (!line.empty()) pa->subset.push_back(line);
     gzclose(f);
   }
+}
+
+// the statistics of --decay_ld, in TSV column order (bit k = column 4 + k)
+const char *const kDecayFields[4] = {"r2_ExpG", "D", "Dp", "r2"};
+
+void check_decay_args(const Params &pars, DecayArgs *da) {
+  if (!da->given) return;
+  if (da->out == nullptr && da->fit == nullptr) error(__FUNCTION__, "the --decay_* options need --decay_out FILE or --decay_fit FILE!");
+  if (da->out != nullptr && *da->out == 0) error(__FUNCTION__, "--decay_out needs a file name!");
+  if (da->fit != nullptr && *da->fit == 0) error(__FUNCTION__, "--decay_fit needs a file name!");
+  ngsld_decay_params &p = da->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.bin_size = 250;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  if (da->ld) {
+    p.fields = 0;
+    const std::string txt = da->ld;
+    size_t b = 0;
+    while (true) {
+      const size_t e = std::min(txt.find(',', b), txt.size());
+      const std::string name = txt.substr(b, e - b);
+      int f = -1;
+      for (int k = 0; k < 4; ++k)
+        if (name == kDecayFields[k]) f = k;
+      if (f < 0) error(__FUNCTION__, "--decay_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+      p.fields |= 1u << f;
+      if (e == txt.size()) break;
+      b = e + 1;
+    }
+  }
+  if (da->bin_size && (!parse_double(da->bin_size, &p.bin_size) || !(p.bin_size > 1) || std::isinf(p.bin_size)))
+    error(__FUNCTION__, "--decay_bin_size must be a number > 1!");
+  if (da->max_kb_dist && (!parse_double(da->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
+    error(__FUNCTION__, "--decay_max_kb_dist must be a number >= 0 (or inf)!");
+  if (da->min_maf && (!parse_double(da->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
+    error(__FUNCTION__, "--decay_min_maf must be a number >= 0!");
+  if (da->n_ind && (!parse_double(da->n_ind, &da->n_ind_v) || da->n_ind_v < 0 || std::isinf(da->n_ind_v)))
+    error(__FUNCTION__, "--decay_n_ind must be a number >= 0!");
+  if (da->recomb_rate && (!parse_double(da->recomb_rate, &da->recomb_rate_v) || !(da->recomb_rate_v > 0) || std::isinf(da->recomb_rate_v)))
+    error(__FUNCTION__, "--decay_recomb_rate must be a number > 0!");
+  if (da->n_ind_v > 0 && (p.fields & (1u | 8u)) == 0) error(__FUNCTION__, "--decay_n_ind is only used for the r2 and r2_ExpG fits!");
+  if (da->n_ind_v > 0 && da->fit != nullptr && (p.fields & 4u))
+    error(__FUNCTION__, "--decay_n_ind cannot be combined with a Dp fit!");
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--decay_out runs on one device: it cannot be combined with --devices!");
+}
+
+FILE *open_or_die(const char *path) {
+  FILE *f = fopen(path, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
+  return f;
+}
+
+void run_decay(ngsld_ctx *ctx, const Params &pars, DecayArgs &da) {
+  ngsld_decay_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_decay(ctx, &da.p, &st) != NGSLD_OK) error("ngsld_decay", ngsld_last_error(ctx));
+  std::vector<int> fields;
+  for (int k = 0; k < 4; ++k)
+    if ((da.p.fields >> k) & 1u) fields.push_back(k);
+  const size_t nf = fields.size();
+  const uint64_t nb = st.bins;
+  std::vector<double> dist(nb), mean(nb * nf);
+  std::vector<uint64_t> count(nb);
+  if (ngsld_decay_bins(ctx, nb, dist.data(), count.data(), mean.data(), nullptr) != NGSLD_OK)
+    error("ngsld_decay_bins", ngsld_last_error(ctx));
+  if (da.out) {  // one line per non-empty bin: its lower break, rows, a mean per statistic (17 digits: the doubles themselves)
+    FILE *f = open_or_die(da.out);
+    fprintf(f, "dist\tn");
+    for (int k : fields) fprintf(f, "\t%s", kDecayFields[k]);
+    fprintf(f, "\n");
+    for (uint64_t i = 0; i < nb; ++i) {
+      fprintf(f, "%.15g\t%lu", dist[i], (unsigned long)count[i]);
+      for (size_t v = 0; v < nf; ++v) fprintf(f, "\t%.17g", mean[i * nf + v]);
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay output file!");
+  }
+  if (da.fit) {  // one line per fitted statistic (D has no model)
+    if (nb == 0) error(__FUNCTION__, "no pair falls in a decay bin: nothing to fit!");
+    std::vector<std::string> lines;
+    for (size_t v = 0; v < nf; ++v) {
+      if (fields[v] == 1) continue;
+      std::vector<double> y(nb);
+      for (uint64_t i = 0; i < nb; ++i) y[i] = mean[i * nf + v];
+      ngsld_decay_fit_result r{};
+      if (ngsld_host_decay_fit(nb, dist.data(), y.data(), 4 + fields[v], da.n_ind_v, da.recomb_rate_v, &r) != NGSLD_OK) {
+        const std::string msg = std::string("the ") + kDecayFields[fields[v]] +
+                                " fit is not defined on these bins (Dp: a bin beyond 10^6 / recomb_rate bp)!";
+        error(__FUNCTION__, msg.c_str());
+      }
+      char buf[512];
+      std::snprintf(buf, sizeof(buf), "%s\t%.17g\t%.17g\t%.17g\t%.17g\t%lu\n", kDecayFields[fields[v]], r.rate, r.ld_max, r.ld_min,
+                    r.sse, (unsigned long)r.n_bins);
+      lines.push_back(buf);
+    }
+    FILE *f = open_or_die(da.fit);
+    fprintf(f, "LD\tDecayRate\tLDmax\tLDmin\tSSE\tn_bins\n");
+    for (const std::string &l : lines) fputs(l.c_str(), f);
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay fit file!");
+  }
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)st.pairs_counted,
+            (unsigned long)st.pairs);
 }
 
 // labels one per line, in site order; a name ending in .gz is written gzip-compressed
@@ -675,9 +808,12 @@ int main(int argc, char **argv) {
   Params pars;
   PruneArgs prune;
   take_prune_args(&argc, argv, &prune);
+  DecayArgs decay;
+  take_decay_args(&argc, argv, &decay);
   parse_cmd_args(&pars, argc, argv);
   check_prune_args(pars, &prune);
-  const bool write_tsv = !prune.given || pars.out != NULL;  // --prune_out without --out: no TSV
+  check_decay_args(pars, &decay);
+  const bool write_tsv = !(prune.given || decay.given) || pars.out != NULL;  // --prune_out / --decay_out without --out: no TSV
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -816,6 +952,8 @@ int main(int argc, char **argv) {
   }
   if (slab_sites > 0 && prune.given)
     error(__FUNCTION__, "--prune_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  if (slab_sites > 0 && decay.given)
+    error(__FUNCTION__, "--decay_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -957,6 +1095,10 @@ int main(int argc, char **argv) {
   if (prune.given) {  // (a second pass of the pair kernels when the TSV was written too)
     run_prune(ctx, pars, prune, pos);
     timing_report.mark("pruning");
+  }
+  if (decay.given) {  // (a pass of the pair kernels of its own)
+    run_decay(ctx, pars, decay);
+    timing_report.mark("LD decay");
   }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)

@@ -1,0 +1,416 @@
+// decay.hip -- LD decay on the device (ngsld_decay, include/ngsld.h): the bins scripts/fit_LDdecay.R averages, from the pair
+// records where they are computed -- no TSV; a few hundred bin means leave the device.  DECAY.md has the rule, the deviations
+// and why the sums are exact.
+//
+//   pairs    ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into context-owned records (run_record_chunks,
+//            shared with ngsld_prune: replayed pairs carry their replayed values)
+//   bins     one wavefront per work item, one lane per candidate (ld_text.hip's mapping): the filters, dist as the TSV prints it,
+//            the right-closed bin, each chosen field as its printed value in integer micro-units (ld_prune.h).  dist rises with
+//            the candidate, so a wavefront's lanes fall in a few runs of one bin: a segmented scan merges each run and its last
+//            lane adds once, into a per-workgroup LDS histogram flushed once per workgroup (when it fits) or into global memory
+//   host     a chunk's int64 sums fold into 128-bit totals; a bin's mean is the double nearest to sum / (10^6 * rows)
+#include "engine.h"
+#include "ld_prune.h"
+
+namespace {
+
+// records of one chunk of rows (32 B each): with |q| < 2^38, a chunk's sum stays below 2^62
+constexpr uint64_t kChunkPairs = 1ull << 24;
+// per-workgroup LDS for the histogram (configs[2]: 400 bins x (1 + 4 fields) x 8 B = 16 KB)
+constexpr uint32_t kLdsBudget = 32u << 10;
+// bins sized from the plan beyond this are refused (raise the bin size or set max_kb_dist): 2^22 bins of 250 bp span 10^9 bp
+constexpr uint64_t kMaxSlots = 1ull << 22;
+
+struct BinArgs {
+  const ngsld_item *items;
+  uint64_t n_items;
+  uint64_t out_base;          // global index of the chunk's record 0
+  const ngsld_rec_std *rec;
+  const double *cum;
+  const uint32_t *infc;
+  const uint8_t *maf_ok;      // printed maf >= min_maf, per site
+  double limit;               // dist < limit (+inf: no limit)
+  double bin;                 // bin size B
+  uint32_t n_slots;           // bins 0 .. n_slots-1
+  int ns;                     // chosen fields
+  int field[4];               // 0 r2_ExpG, 1 D, 2 D', 3 r2
+  int track_max;              // a chunk of more than kChunkPairs pairs: max |q| goes to meta[1]
+  unsigned long long *acc;    // [(1 + ns) * n_slots]: rows per bin, then the int64 sums of each field (two's complement)
+  unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|, [2] a bin beyond n_slots
+};
+
+// dist as the TSV prints it ("%.0f", read back): the exact binary value rounded half-to-even (exact for integer gaps)
+__host__ __device__ inline double printed_dist(double x) { return __builtin_rint(x); }
+
+// the right-closed bin (k*B, (k+1)*B] of d, with the breaks computed as R's seq(0, ., B) does (k * B); -1 for d <= 0
+__host__ __device__ inline long long bin_of(double d, double B) {
+  if (!(d > 0.0)) return -1;
+  long long k = (long long)__builtin_ceil(d / B) - 1;
+  if (k < 0) k = 0;
+  while (k > 0 && !(d > (double)k * B)) --k;
+  while (d > (double)(k + 1) * B) ++k;
+  return k;
+}
+
+__device__ __forceinline__ double field_of(const ngsld_rec_std &r, int f) {
+  return f == 0 ? r.r2_ExpG : f == 1 ? r.D : f == 2 ? r.Dp : r.r2;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
+  extern __shared__ unsigned long long lds[];
+  const uint32_t W = (uint32_t)(1 + A.ns) * A.n_slots;
+  unsigned long long *acc = kLds ? lds : A.acc;
+  if (kLds) {
+    for (uint32_t j = threadIdx.x; j < W; j += 256) lds[j] = 0;
+    __syncthreads();
+  }
+  const int lane = (int)__lane_id();
+  const uint64_t waves = (uint64_t)gridDim.x * 4;
+  unsigned long long qmax = 0;
+  for (uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6; i < A.n_items; i += waves) {
+    const ngsld_item it = A.items[i];
+    const uint32_t c = (uint32_t)lane;
+    long long key = 0x7fffffffffffffffll;  // past the row (or its chromosome): one run at the tail
+    bool take = false;
+    long long q[4] = {0, 0, 0, 0};
+    if (c < it.count) {
+      const uint32_t s1 = it.s1, s2 = it.s2_begin + c;
+      if (A.infc[s1] == A.infc[s2]) {  // (across a chromosome dist is not finite: never counted)
+        const double d = printed_dist(A.cum[s2] - A.cum[s1]);
+        key = bin_of(d, A.bin);
+        if (((it.mask >> c) & 1ull) && key >= 0 && d < A.limit && A.maf_ok[s1] && A.maf_ok[s2]) {
+          const uint64_t k = it.first_record - A.out_base + (uint64_t)__popcll(it.mask & ((1ull << c) - 1ull));
+          const ngsld_rec_std r = A.rec[k];
+          take = true;
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            if (v >= A.ns) break;
+            const double x = field_of(r, A.field[v]);
+            if (!(x - x == 0.0)) take = false;  // NaN or +-inf in any chosen field: the row drops out of every one
+          }
+          if (take) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+              if (v >= A.ns) break;
+              int64_t m = 0;
+              if (!ngsld::printed_micro(field_of(r, A.field[v]), &m)) {
+                atomicCAS(A.meta, 0ull, (((unsigned long long)s1 << 32) | s2) + 1ull);
+                take = false;
+              }
+              q[v] = m;
+            }
+          }
+          if (!take) q[0] = q[1] = q[2] = q[3] = 0;
+        }
+      }
+    }
+    if (__ballot(take) == 0) continue;
+    if (A.track_max) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (v >= A.ns) break;
+        const unsigned long long a = (unsigned long long)(q[v] < 0 ? -q[v] : q[v]);
+        qmax = a > qmax ? a : qmax;
+      }
+    }
+    // runs of one key, numbered from lane 0 (keys rise with the lane; the numbering does not rely on it)
+    const long long prev = __shfl_up(key, 1);
+    const uint64_t heads = __ballot(lane == 0 || prev != key);
+    const uint32_t run = (uint32_t)__popcll(heads & ((2ull << lane) - 1ull));
+    const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+    uint32_t cnt = take ? 1u : 0u;
+    for (int o = 1; o < 64; o <<= 1) {  // segmented inclusive scan: the run's last lane holds its totals
+      const uint32_t ro = __shfl_up(run, o);  // (every lane takes part in every shuffle)
+      const bool add = lane >= o && ro == run;
+      const uint32_t co = __shfl_up(cnt, o);
+      if (add) cnt += co;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (v >= A.ns) break;
+        const long long qo = __shfl_up(q[v], o);
+        if (add) q[v] += qo;
+      }
+    }
+    if (last && cnt > 0) {
+      if (key >= 0 && key < (long long)A.n_slots) {
+        atomicAdd(acc + key, (unsigned long long)cnt);
+        for (int v = 0; v < A.ns; ++v) atomicAdd(acc + (uint64_t)(1 + v) * A.n_slots + key, (unsigned long long)q[v]);
+      } else {
+        atomicOr(A.meta + 2, 1ull);
+      }
+    }
+  }
+  if (A.track_max) {
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long x = __shfl_xor(qmax, o);
+      qmax = x > qmax ? x : qmax;
+    }
+    if (lane == 0 && qmax) atomicMax(A.meta + 1, qmax);
+  }
+  if (kLds) {
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < W; j += 256)
+      if (lds[j] != 0) atomicAdd(A.acc + j, lds[j]);
+  }
+}
+
+inline unsigned blocks_for(uint64_t threads, unsigned per_block = 256) { return (unsigned)((threads + per_block - 1) / per_block); }
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the double nearest to a / b (round half to even) for a >= 0, 0 < b < 2^126 and a / b < 2^54 (a mean below 2^38 / 10^6):
+// long division to 55 significant bits, then the round bit and the sticky remainder
+double div_nearest(unsigned __int128 a, unsigned __int128 b) {
+  if (a == 0) return 0.0;
+  unsigned __int128 q = a / b, r = a % b;
+  int sh = 0;  // a / b = (q + r / b) * 2^-sh
+  while (q < ((unsigned __int128)1 << 54)) {
+    r <<= 1;
+    q <<= 1;
+    if (r >= b) {
+      r -= b;
+      q |= 1;
+    }
+    ++sh;
+  }
+  bool sticky = r != 0;
+  const unsigned low = (unsigned)(q & 3);
+  uint64_t m = (uint64_t)(q >> 2);
+  sticky = sticky || (low & 1);
+  if ((low & 2) && (sticky || (m & 1))) ++m;
+  return std::ldexp((double)m, 2 - sh);
+}
+
+// R's as.character of a break (15 significant digits) read back
+double break_value(uint64_t k, double B) {
+  char buf[64];
+  std::snprintf(buf, sizeof(buf), "%.15g", (double)k * B);
+  return std::strtod(buf, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *stats) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  const auto t_all = std::chrono::steady_clock::now();
+  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+  if (p == nullptr || p->struct_size != sizeof(ngsld_decay_params))
+    return fail(c, NGSLD_ERR_INVALID, "ngsld_decay_params: struct_size must be sizeof(ngsld_decay_params)");
+  if (stats != nullptr && stats->struct_size < sizeof(uint32_t)) return fail(c, NGSLD_ERR_INVALID, "ngsld_decay_stats: struct_size not set");
+  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "decay fields must be a non-empty mask of 1, 2, 4, 8");
+  if (!(p->bin_size > 1.0) || !std::isfinite(p->bin_size)) return fail(c, NGSLD_ERR_INVALID, "decay bin_size must be a finite number > 1");
+  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "decay max_kb_dist must be >= 0");
+  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "decay min_maf is NaN");
+  const uint64_t n = c->n_sites;
+  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->decay_fields = 0;
+  c->decay_dist.clear();
+  c->decay_mean.clear();
+  c->decay_count.clear();
+  ngsld_decay_stats S;
+  std::memset(&S, 0, sizeof(S));
+  S.struct_size = sizeof(S);
+  hipStream_t st = c->stream;
+  int field[4] = {0, 0, 0, 0}, ns = 0;
+  for (int f = 0; f < 4; ++f)
+    if ((p->fields >> f) & 1u) field[ns++] = f;
+  const double B = p->bin_size;
+
+  // ---- sites: dist prefix sums (ld_text.hip's), the maf filter on the printed maf ----
+  const double limit = p->max_kb_dist * 1000.0;
+  std::vector<double> cum(n);
+  std::vector<uint32_t> infc(n);
+  std::vector<uint8_t> maf_ok(n);
+  bool exact_gaps = true;  // integer gaps >= 0
+  {
+    double run = 0.0;
+    uint32_t ic = 0;
+    bool &exact = exact_gaps;
+    for (uint64_t s = 0; s < n; ++s) {
+      const double g = c->h_pos_dist.size() == n ? c->h_pos_dist[s] : std::numeric_limits<double>::infinity();
+      if (std::isinf(g) && g > 0) {
+        ++ic;
+      } else {
+        if (!(g >= 0.0) || g != std::floor(g) || run + g > 9.0e15) exact = false;
+        run += g;
+      }
+      cum[s] = run;
+      infc[s] = ic;
+      const double m = c->h_maf[s];
+      maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes, as in R)
+    }
+    if (!exact && std::isfinite(limit))
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "decay max_kb_dist needs integer position gaps");
+  }
+
+  // ---- bins sized from the plan: the largest finite planned dist, capped by the limit ----
+  uint64_t n_slots = 0;
+  {
+    std::vector<uint64_t> chr_last(n ? (size_t)infc[n - 1] + 1 : 0, 0);
+    std::vector<double> chr_lo(chr_last.size(), INFINITY), chr_hi(chr_last.size(), -INFINITY);
+    for (uint64_t s = 0; s < n; ++s) {
+      chr_last[infc[s]] = s;
+      chr_lo[infc[s]] = std::min(chr_lo[infc[s]], cum[s]);
+      chr_hi[infc[s]] = std::max(chr_hi[infc[s]], cum[s]);
+    }
+    double dmax = 0.0;
+    for (uint64_t s1 = 0; s1 < n; ++s1) {
+      if (c->h_row_off[s1 + 1] == c->h_row_off[s1]) continue;
+      const uint64_t s2 = std::min<uint64_t>(c->h_row_end[s1] - 1, chr_last[infc[s1]]);
+      if (s2 <= s1) continue;
+      // gaps >= 0 (every position file): dist rises along the row; any other gaps: the chromosome's span bounds it
+      const double d = exact_gaps ? cum[s2] - cum[s1] : chr_hi[infc[s1]] - chr_lo[infc[s1]];
+      dmax = std::max(dmax, printed_dist(d));
+    }
+    if (dmax >= limit) dmax = limit;  // (dist < limit: the limit's own bin is the last one that can fill)
+    const long long kmax = bin_of(dmax, B);
+    if (kmax >= 0) {
+      if ((uint64_t)kmax >= kMaxSlots)
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "more than 2^22 decay bins (raise bin_size or set max_kb_dist)");
+      n_slots = (uint64_t)kmax + 1;
+    }
+  }
+  S.bin_slots = n_slots;
+  const uint64_t W = (uint64_t)(1 + ns) * n_slots;
+  uint64_t lds_budget = kLdsBudget;
+  if (const char *e = test_knob("DECAY_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), 64u << 10);
+  const bool use_lds = W > 0 && W * 8 <= lds_budget;
+  S.lds = use_lds ? 1 : 0;
+  uint64_t chunk = kChunkPairs;
+  if (const char *e = test_knob("DECAY_CHUNK_PAIRS")) chunk = std::max<uint64_t>(1, std::min<uint64_t>(kChunkPairs, std::strtoull(e, nullptr, 10)));
+
+  const uint64_t n_pairs = c->h_row_off[n];
+  S.pairs = n_pairs;
+  std::vector<unsigned __int128> sum(ns * n_slots, 0);
+  std::vector<uint64_t> count(n_slots, 0);
+  if (n_slots > 0 && n_pairs > 0) {
+    DevBuf<double> d_cum;
+    DevBuf<uint32_t> d_infc;
+    DevBuf<uint8_t> d_maf_ok;
+    DevBuf<unsigned long long> d_acc, d_meta;
+    HIP_TRY(c, d_cum.resize(n));
+    HIP_TRY(c, d_infc.resize(n));
+    HIP_TRY(c, d_maf_ok.resize(n));
+    HIP_TRY(c, d_acc.resize(W));
+    HIP_TRY(c, d_meta.resize(3));
+    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
+    // records: the chunk, or the longest row when one is longer (a row is never cut)
+    uint64_t longest = 0;
+    for (uint64_t s = 0; s < n; ++s) longest = std::max<uint64_t>(longest, c->h_row_off[s + 1] - c->h_row_off[s]);
+    const uint64_t rec_cap = std::max<uint64_t>(std::min<uint64_t>(n_pairs, chunk), longest);
+    DevBuf<ngsld_rec_std> d_rec;
+    HIP_TRY(c, d_rec.resize(rec_cap));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HIP_TRY(c, hipEventCreate(&ev0));
+    HIP_TRY(c, hipEventCreate(&ev1));
+    struct Events {
+      hipEvent_t a, b;
+      ~Events() {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+      }
+    } events_{ev0, ev1};
+    BinArgs A{};
+    A.rec = d_rec.p;
+    A.cum = d_cum.p;
+    A.infc = d_infc.p;
+    A.maf_ok = d_maf_ok.p;
+    A.limit = limit;
+    A.bin = B;
+    A.n_slots = (uint32_t)n_slots;
+    A.ns = ns;
+    for (int v = 0; v < 4; ++v) A.field[v] = field[v];
+    A.acc = d_acc.p;
+    A.meta = d_meta.p;
+    std::vector<unsigned long long> h_acc(W);
+    const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
+    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t np) -> int {
+      A.out_base = c->h_row_off[r0];
+      A.track_max = np > kChunkPairs ? 1 : 0;
+      const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
+      HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
+      HIP_TRY(c, hipEventRecord(ev0, st));
+      const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
+      for (uint64_t off = i0; off < i1; off += max_items) {
+        A.items = c->d_items.p + off;
+        A.n_items = std::min<uint64_t>(max_items, i1 - off);
+        const unsigned blocks = std::min<unsigned>(blocks_for(A.n_items * 64), max_blocks);
+        if (use_lds)
+          hipLaunchKernelGGL(bin_kernel<true>, dim3(blocks), dim3(256), (size_t)W * 8, st, A);
+        else
+          hipLaunchKernelGGL(bin_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+        HIP_TRY(c, hipGetLastError());
+      }
+      HIP_TRY(c, hipEventRecord(ev1, st));
+      unsigned long long meta[3] = {0, 0, 0};
+      HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      float ms = 0.f;
+      HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
+      S.bin_ms += ms;
+      ++S.chunks;
+      if (meta[0] != 0) {
+        const unsigned long long k = meta[0] - 1;
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a decay value of the pair of sites " + std::to_string(k >> 32) + " - " +
+                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
+      }
+      if (meta[2] != 0) return fail(c, NGSLD_ERR_INVALID, "decay: a row fell beyond the planned bins (internal error)");
+      // a row longer than a chunk is one chunk: every partial sum of it is exact when max |q| * pairs < 2^63
+      if (A.track_max && meta[1] > 0 && (unsigned __int128)meta[1] * np >= ((unsigned __int128)1 << 63))
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(np) + " pairs with values too large to sum exactly");
+      for (uint64_t k = 0; k < n_slots; ++k) {
+        count[k] += h_acc[k];
+        for (int v = 0; v < ns; ++v) sum[v * n_slots + k] += (unsigned __int128)(__int128)(int64_t)h_acc[(1 + v) * n_slots + k];
+      }
+      return NGSLD_OK;
+    });
+    if (rc != NGSLD_OK) return rc;
+  }
+
+  // ---- the means: exact integer sums, one rounding ----
+  for (uint64_t k = 0; k < n_slots; ++k) {
+    if (count[k] == 0) continue;
+    c->decay_dist.push_back(break_value(k, B));
+    c->decay_count.push_back(count[k]);
+    S.pairs_counted += count[k];
+    for (int v = 0; v < ns; ++v) {
+      const __int128 s = (__int128)sum[v * n_slots + k];
+      const unsigned __int128 a = (unsigned __int128)(s < 0 ? -s : s), b = (unsigned __int128)count[k] * 1000000u;
+      const double m = div_nearest(a, b);
+      c->decay_mean.push_back(s < 0 ? -m : m);
+    }
+  }
+  c->decay_fields = p->fields;
+  S.bins = c->decay_count.size();
+  S.total_ms = ms_since(t_all);
+  if (stats != nullptr) {
+    const uint32_t want = stats->struct_size;
+    std::memcpy(stats, &S, std::min<size_t>(want, sizeof(S)));
+    stats->struct_size = want;
+  }
+  return NGSLD_OK;
+} NGSLD_CATCH(c)
+
+int ngsld_decay_bins(ngsld_ctx *c, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins) {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  const uint64_t nb = c->decay_count.size();
+  if (n_bins) *n_bins = nb;
+  const uint64_t m = std::min<uint64_t>(cap, nb);
+  const int nf = __builtin_popcount(c->decay_fields);
+  if (m > 0 && dist) std::memcpy(dist, c->decay_dist.data(), m * sizeof(double));
+  if (m > 0 && count) std::memcpy(count, c->decay_count.data(), m * sizeof(uint64_t));
+  if (m > 0 && mean) std::memcpy(mean, c->decay_mean.data(), m * nf * sizeof(double));
+  return NGSLD_OK;
+}
+
+}  // extern "C"

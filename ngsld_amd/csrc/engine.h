@@ -440,6 +440,11 @@ struct ngsld_ctx {
   size_t ev_used = 0;
   hipStream_t timed_stream = nullptr;
   uint64_t timed_pairs = 0;
+
+  // the bins of the last ngsld_decay (ngsld_decay_bins copies them out): lower break, rows, one mean per chosen field
+  uint32_t decay_fields = 0;
+  std::vector<double> decay_dist, decay_mean;  // decay_mean: [bin][field], fields in TSV column order
+  std::vector<uint64_t> decay_count;
 };
 
 namespace ngsld {
@@ -507,6 +512,13 @@ hipError_t timed_launch(ngsld_ctx *c, const PairArgs &a, hipStream_t stream);
 // flag_n: records the flag buffer was laid out for (its two bitmaps follow the list: ld_device.h)
 PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext,
                    uint32_t *d_flags = nullptr, uint32_t flag_cap = 0, uint64_t flag_n = 0);
+
+// Rows [0, n_sites) chunk by chunk into d_rec (room for rec_cap records): chunks of up to chunk_pairs records, a longer row
+// is a chunk of its own (NGSLD_ERR_UNSUPPORTED past rec_cap): ngsld_run_device + ngsld_finish_device on the context's stream, so every record is final (replayed pairs
+// carry their replayed values), then on_chunk(r0, r1, pairs) for the chunk's rows [r0, r1).  *pairs_ms adds the wall time of
+// the pair phase.  ngsld_prune and ngsld_decay read the records this way.
+int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
+                      const std::function<int(uint64_t r0, uint64_t r1, uint64_t pairs)> &on_chunk);
 
 // ---- engine_replay.hip ----
 // send_flag_rows: for the pairs a text batch leaves to the host (its flag list, or its host-only list behind a device-side

@@ -1029,6 +1029,28 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
   }
   return check_status(c);
 }
+
+int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
+                      const std::function<int(uint64_t, uint64_t, uint64_t)> &on_chunk) {
+  const uint64_t n = c->n_sites;
+  for (uint64_t r0 = 0; r0 < n;) {
+    uint64_t r1 = r0 + 1;
+    while (r1 < n && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
+    const uint64_t np = c->h_row_off[r1] - c->h_row_off[r0];
+    if (np > rec_cap) return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(np) + " pairs does not fit the record buffer");
+    if (np > 0) {
+      const auto t0 = std::chrono::steady_clock::now();
+      int rc = ngsld_run_device(c, r0, r1, d_rec, nullptr, nullptr);  // (the ctx's stream: records final, replay done)
+      if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
+      if (rc != NGSLD_OK) return rc;
+      if (pairs_ms) *pairs_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      rc = on_chunk(r0, r1, np);
+      if (rc != NGSLD_OK) return rc;
+    }
+    r0 = r1;
+  }
+  return NGSLD_OK;
+}
 }  // namespace eng
 }  // namespace ngsld
 

@@ -1,5 +1,6 @@
 // ld_prune.h -- the edge weight of LD pruning, shared by the device's edge extraction (prune.hip) and the host
-// (prune_host.cpp: ngsld_host_prune_label, ngsld_host_prune_graph).  Not part of the ld_device.h umbrella: the pair kernels
+// (prune_host.cpp: ngsld_host_prune_label, ngsld_host_prune_graph), and the printed value in micro-units that LD decay's bins
+// sum (decay.hip).  Not part of the ld_device.h umbrella: the pair kernels
 // never see it.
 //
 // A pruner that reads the TSV sees every value "as printed": the double nearest to its "%f" text.  Both glibc and the
@@ -19,12 +20,11 @@
 
 namespace ngsld {
 
-// the double a reader gets back from "%f" of a finite x
-NGSLD_PRUNE_HD inline double prune_printed(double x) {
+// round_half_even(|x| * 10^6) computed exactly: the digits of "%f" of |x| without the point, for a finite |x| < 2^33
+NGSLD_PRUNE_HD inline uint64_t printed_micro_abs(double x) {
   uint64_t bits;
   __builtin_memcpy(&bits, &x, sizeof(bits));
   const int ebits = (int)((bits >> 52) & 0x7ff);
-  if (ebits >= 1023 + 33) return x;  // |x| >= 2^33 (and inf / NaN, which the callers have sorted out)
   uint64_t m = bits & 0xfffffffffffffull;
   int ex;  // |x| = m * 2^ex, ex <= -20 here
   if (ebits == 0) {
@@ -42,8 +42,28 @@ NGSLD_PRUNE_HD inline double prune_printed(double x) {
     const unsigned __int128 rem = M - (quo << k), half = (unsigned __int128)1 << (k - 1);
     if (rem > half || (rem == half && (q & 1))) ++q;
   }
-  const double p = (double)q / 1e6;
+  return q;
+}
+
+// the double a reader gets back from "%f" of a finite x
+NGSLD_PRUNE_HD inline double prune_printed(double x) {
+  uint64_t bits;
+  __builtin_memcpy(&bits, &x, sizeof(bits));
+  if ((int)((bits >> 52) & 0x7ff) >= 1023 + 33) return x;  // |x| >= 2^33 (and inf / NaN, which the callers have sorted out)
+  const double p = (double)printed_micro_abs(x) / 1e6;
   return (bits >> 63) ? -p : p;
+}
+
+// LD decay's exact accumulator (decay.hip): q = round_half_even(x * 10^6), the printed value in integer micro-units, for a
+// finite x.  false when |q| would reach 2^38 (|x| >~ 2.7 * 10^5): never wrapped.
+NGSLD_PRUNE_HD inline bool printed_micro(double x, int64_t *q) {
+  uint64_t bits;
+  __builtin_memcpy(&bits, &x, sizeof(bits));
+  if ((int)((bits >> 52) & 0x7ff) >= 1023 + 19) return false;  // |x| >= 2^19: |q| > 5 * 10^11 > 2^38
+  const uint64_t a = printed_micro_abs(x);
+  if (a >= (1ull << 38)) return false;
+  *q = (bits >> 63) ? -(int64_t)a : (int64_t)a;
+  return true;
 }
 
 // 10^prec as a double (exact for the supported 0 <= prec <= 15)

@@ -364,52 +364,43 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   A.meta = d_meta.p;
   A.rec = d_rec.p;
   unsigned long long meta[4] = {0, 0, 0, 0};
-  for (uint64_t r0 = 0; r0 < n;) {
-    uint64_t r1 = r0 + 1;
-    while (r1 < n && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
-    const uint64_t np = c->h_row_off[r1] - c->h_row_off[r0];
-    if (np > 0) {
-      auto t0 = std::chrono::steady_clock::now();
-      int rc = ngsld_run_device(c, r0, r1, d_rec.p, nullptr, nullptr);  // (the ctx's stream: records final, replay done)
-      if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
-      if (rc != NGSLD_OK) return rc;
-      S.pairs_ms += ms_since(t0);
-      // room for every pair of this chunk to be an edge
-      const uint64_t need = meta[0] + np;
-      if (d_el.n < need) {
-        const size_t cap = (size_t)std::max<uint64_t>(need, std::min<uint64_t>(n_pairs, 2 * (uint64_t)d_el.n));
-        HIP_TRY(c, grow(d_ea, cap, meta[0], st));
-        HIP_TRY(c, grow(d_eb, cap, meta[0], st));
-        HIP_TRY(c, grow(d_el, cap, meta[0], st));
-      }
-      A.ea = d_ea.p;
-      A.eb = d_eb.p;
-      A.el = d_el.p;
-      A.cap = d_el.n;
-      A.out_base = c->h_row_off[r0];
-      const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-      HIP_TRY(c, hipEventRecord(ev0, st));
-      const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
-      for (uint64_t off = i0; off < i1; off += max_items) {
-        A.items = c->d_items.p + off;
-        A.n_items = std::min<uint64_t>(max_items, i1 - off);
-        hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(A.n_items * 64)), dim3(256), 0, st, A);
-        HIP_TRY(c, hipGetLastError());
-      }
-      HIP_TRY(c, hipEventRecord(ev1, st));
-      HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      float ms = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
-      S.edges_ms += ms;
-      if (meta[3] != 0) {
-        const unsigned long long k = meta[3] - 1;
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "the edge label of the pair " + lab[k >> 32] + " - " + lab[k & 0xffffffffull] +
-                                                  " reaches 2^62 (lower the precision)");
-      }
+  const int rc_chunks = run_record_chunks(c, chunk_pairs, d_rec.p, chunk_pairs, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t np) -> int {
+    // room for every pair of this chunk to be an edge
+    const uint64_t need = meta[0] + np;
+    if (d_el.n < need) {
+      const size_t cap = (size_t)std::max<uint64_t>(need, std::min<uint64_t>(n_pairs, 2 * (uint64_t)d_el.n));
+      HIP_TRY(c, grow(d_ea, cap, meta[0], st));
+      HIP_TRY(c, grow(d_eb, cap, meta[0], st));
+      HIP_TRY(c, grow(d_el, cap, meta[0], st));
     }
-    r0 = r1;
-  }
+    A.ea = d_ea.p;
+    A.eb = d_eb.p;
+    A.el = d_el.p;
+    A.cap = d_el.n;
+    A.out_base = c->h_row_off[r0];
+    const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
+    HIP_TRY(c, hipEventRecord(ev0, st));
+    const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
+    for (uint64_t off = i0; off < i1; off += max_items) {
+      A.items = c->d_items.p + off;
+      A.n_items = std::min<uint64_t>(max_items, i1 - off);
+      hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(A.n_items * 64)), dim3(256), 0, st, A);
+      HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(ev1, st));
+    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
+    S.edges_ms += ms;
+    if (meta[3] != 0) {
+      const unsigned long long k = meta[3] - 1;
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "the edge label of the pair " + lab[k >> 32] + " - " + lab[k & 0xffffffffull] +
+                                                " reaches 2^62 (lower the precision)");
+    }
+    return NGSLD_OK;
+  });
+  if (rc_chunks != NGSLD_OK) return rc_chunks;
   d_rec.release();
   const uint64_t E = meta[0];
   S.edges = E;
