@@ -288,6 +288,22 @@ int ngsld_set_tuning(ngsld_ctx *ctx, uint32_t pairs_per_item, uint64_t batch_pai
  * reduction, refined reciprocal).  Returns NGSLD_OK or NGSLD_ERR_DEVICE with a message. */
 int ngsld_selftest(ngsld_ctx *ctx);
 
+/* On-device self test of the text formatter: n rows, row i the pair (2i, 2i+1) of a batch of 2n sites with the records
+ * std[i] (and ext[i]; ext NULL: standard rows), the printed dist dist[i] (+INFINITY: a chromosome change) and the site
+ * frequencies maf1[i], maf2[i]; labels print as "(null)".  The rows go through the production passes (lengths, prefix sums,
+ * write) into text (text_cap bytes: NGSLD_ERR_INVALID when they do not fit), row_len[n] receives each row's length and
+ * *needs_host 1 when a value lies beyond the device formatter, as a run would hand that batch over as records.  Host
+ * pointers. */
+int ngsld_selftest_format(ngsld_ctx *ctx, uint64_t n, const ngsld_rec_std *std, const ngsld_rec_ext *ext, const double *dist,
+                          const double *maf1, const double *maf2, char *text, uint64_t text_cap, uint64_t *row_len,
+                          int32_t *needs_host);
+/* On-device self test of the printed-value quantiser (PRUNE.md, DECAY.md), for n doubles x[]: micro[i] / micro_ok[i] what LD
+ * decay's bin kernel sums for x[i] (its "%f" in integer micro-units; ok 0 from 2^38 on), label[i] / label_rc[i] the edge label
+ * LD pruning gives it with the weight type ('a', 'e', 'n'), precision (0..15) and min_weight (rc 0 an edge, 1 skipped, 2 a label
+ * of 2^62 or more).  Host pointers. */
+int ngsld_selftest_printed(ngsld_ctx *ctx, uint64_t n, const double *x, int32_t precision, int32_t weight_type,
+                           double min_weight, int64_t *micro, int32_t *micro_ok, int64_t *label, int32_t *label_rc);
+
 /* ---- Streaming: matrices larger than the device budget (windowed runs only) ------------------------------
  * The reference keeps the whole matrix in host memory (twice during the transpose, ngsLD.cpp:87-89).  Here a
  * windowed run (max_kb_dist and/or max_snp_dist > 0) can be cut into slabs of rows: slab k holds the sites

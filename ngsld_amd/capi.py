@@ -85,7 +85,8 @@ SYMBOLS = [
     "ngsld_set_replay_source", "ngsld_set_replay_matrix", "ngsld_set_replay", "ngsld_replay_stats", "ngsld_finish_device",
     "ngsld_set_exact_store", "ngsld_replay_info",
     "ngsld_plan_parts", "ngsld_run_multi", "ngsld_multi_last_distribution", "ngsld_rccl_selftest",
-    "ngsld_last_kernel_time", "ngsld_pair_kernel", "ngsld_describe_dispatch", "ngsld_set_tuning", "ngsld_selftest", "ngsld_reserve_text_buffers",
+    "ngsld_last_kernel_time", "ngsld_pair_kernel", "ngsld_describe_dispatch", "ngsld_set_tuning", "ngsld_selftest", "ngsld_selftest_format",
+    "ngsld_selftest_printed", "ngsld_reserve_text_buffers",
     "ngsld_window_ends", "ngsld_plan_slabs", "ngsld_slab_sites_for_budget", "ngsld_sites_for_budget", "ngsld_streamed_replay_info", "ngsld_set_memory_budget", "ngsld_device_memory", "ngsld_run_streamed", "ngsld_run_streamed_text",
     "ngsld_host_read_geno_bin_range",
     "ngsld_host_set_threads", "ngsld_host_read_pos", "ngsld_host_pos_dist", "ngsld_host_label", "ngsld_host_free_pos", "ngsld_host_pos_slice",
@@ -202,6 +203,9 @@ def lib() -> C.CDLL:
             L.ngsld_pair_kernel.argtypes = [vp]
             L.ngsld_pair_kernel.restype = C.c_char_p
         L.ngsld_selftest.argtypes = [vp]
+        if hasattr(L, "ngsld_selftest_format"):
+            L.ngsld_selftest_format.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.c_char_p, u64, vp, C.POINTER(C.c_int32)]
+            L.ngsld_selftest_printed.argtypes = [vp, u64, vp, C.c_int32, C.c_int32, dbl, vp, vp, vp, vp]
         L.ngsld_window_ends.argtypes = [vp, u64, C.POINTER(Params), vp]
         L.ngsld_plan_slabs.argtypes = [vp, u64, C.POINTER(Params), u64, vp, u64, C.POINTER(u64)]
         L.ngsld_slab_sites_for_budget.argtypes = [u64, u64]
@@ -713,6 +717,37 @@ class Engine:
 
     def selftest(self) -> None:
         self._check(self._L.ngsld_selftest(self._h))
+
+    def selftest_format(self, std_rec: np.ndarray, ext_rec: np.ndarray | None, dist, maf1, maf2) -> tuple[list[str], bool]:
+        """The device's TSV rows of n records (ngsld_selftest_format): row i the pair of sites (2i, 2i+1) with labels "(null)",
+        dist[i] as its dist column (inf: a chromosome change) and maf1[i], maf2[i].  Returns (rows, needs_host)."""
+        std_rec = np.ascontiguousarray(std_rec, dtype=REC_STD)
+        n = len(std_rec)
+        ext = None if ext_rec is None else np.ascontiguousarray(ext_rec, dtype=REC_EXT)
+        assert ext is None or len(ext) == n
+        d, m1, m2 = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for v in (dist, maf1, maf2))
+        cap = n * (400 if ext is None else 1200)
+        text = C.create_string_buffer(cap)
+        lens = np.zeros(n, dtype=np.uint64)
+        host = C.c_int32()
+        self._check(self._L.ngsld_selftest_format(self._h, n, std_rec.ctypes.data, None if ext is None else ext.ctypes.data,
+                                                  d.ctypes.data, m1.ctypes.data, m2.ctypes.data, text, cap, lens.ctypes.data,
+                                                  C.byref(host)))
+        raw = text.raw[:int(lens.sum())].decode()
+        ends = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        return [raw[ends[i]:ends[i + 1]] for i in range(n)], bool(host.value)
+
+    def selftest_printed(self, x, precision: int = 4, weight_type: str = "a", min_weight: float = 0.0) -> dict:
+        """The device's printed-value quantiser (ngsld_selftest_printed) on the doubles x: arrays "micro" / "micro_ok" (LD
+        decay's integer micro-units) and "label" / "rc" (LD pruning's edge label: rc 0 an edge, 1 skipped, 2 too large)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = len(x)
+        out = {"micro": np.zeros(n, dtype=np.int64), "micro_ok": np.zeros(n, dtype=np.int32), "label": np.zeros(n, dtype=np.int64),
+               "rc": np.zeros(n, dtype=np.int32)}
+        self._check(self._L.ngsld_selftest_printed(self._h, n, x.ctypes.data, precision, ord(weight_type), float(min_weight),
+                                                   out["micro"].ctypes.data, out["micro_ok"].ctypes.data,
+                                                   out["label"].ctypes.data, out["rc"].ctypes.data))
+        return out
 
     def set_geno_raw(self, gl, n_sites: int | None = None, n_ind: int | None = None, log_scale: bool = False,
                      ignore_miss_data: bool = False, text: bool = False, call_geno: tuple | None = None,

@@ -230,7 +230,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
 
 extern "C" {
 
-const char *ngsld_version(void) { return "ngsld-amd 0.6.0 (gfx950; reference ngsLD 1.2.1)"; }
+const char *ngsld_version(void) { return "ngsld-amd 0.7.0 (gfx950; reference ngsLD 1.2.1)"; }
 
 int ngsld_create(int device, ngsld_ctx **out) {
   if (out == nullptr) return NGSLD_ERR_INVALID;
@@ -467,6 +467,93 @@ int ngsld_selftest(ngsld_ctx *c) try {
   }
   return NGSLD_OK;
 } NGSLD_CATCH(c)
+
+int ngsld_selftest_format(ngsld_ctx *c, uint64_t n, const ngsld_rec_std *std_rec, const ngsld_rec_ext *ext_rec, const double *dist,
+                          const double *maf1, const double *maf2, char *text, uint64_t text_cap, uint64_t *row_len,
+                          int32_t *needs_host) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  if (n == 0 || n > (1ull << 24) || std_rec == nullptr || dist == nullptr || maf1 == nullptr || maf2 == nullptr ||
+      text == nullptr || row_len == nullptr || needs_host == nullptr)
+    return fail(c, NGSLD_ERR_INVALID, "ngsld_selftest_format: 1 <= n <= 2^24 rows and every pointer but ext set");
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  // row i: the pair (2i, 2i+1), alone in its item; cum / infc make cum[s2] - cum[s1] == dist[i] exactly, +inf a chromosome change
+  std::vector<ngsld_item> items(n);
+  std::vector<double> cum(2 * n, 0.0), maf(2 * n);
+  std::vector<uint32_t> infc(2 * n, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    items[i] = ngsld_item{(uint32_t)(2 * i), (uint32_t)(2 * i + 1), 1, 0, 1ull, i};
+    if (dist[i] == std::numeric_limits<double>::infinity())
+      infc[2 * i + 1] = 1;
+    else
+      cum[2 * i + 1] = dist[i];
+    maf[2 * i] = maf1[i];
+    maf[2 * i + 1] = maf2[i];
+  }
+  DevBuf<ngsld_item> d_items;
+  DevBuf<ngsld_rec_std> d_std;
+  DevBuf<ngsld_rec_ext> d_ext;
+  DevBuf<double> d_cum, d_maf;
+  DevBuf<uint32_t> d_infc;
+  DevBuf<uint64_t> d_lens, d_offs, d_meta;  // meta: [0] total length, [1] overflow
+  DevBuf<int> d_host;
+  DevBuf<char> d_text, d_tmp;
+  const size_t tmp_bytes = text_scan_temp_bytes(n);
+  HIP_TRY(c, d_items.resize(n));
+  HIP_TRY(c, d_std.resize(n));
+  if (ext_rec != nullptr) HIP_TRY(c, d_ext.resize(n));
+  HIP_TRY(c, d_cum.resize(2 * n));
+  HIP_TRY(c, d_maf.resize(2 * n));
+  HIP_TRY(c, d_infc.resize(2 * n));
+  HIP_TRY(c, d_lens.resize(n));
+  HIP_TRY(c, d_offs.resize(n));
+  HIP_TRY(c, d_meta.resize(2));
+  HIP_TRY(c, d_host.resize(1));
+  HIP_TRY(c, d_text.resize(text_cap ? text_cap : 1));
+  HIP_TRY(c, d_tmp.resize(tmp_bytes ? tmp_bytes : 1));
+  HIP_TRY(c, hipMemcpy(d_items.p, items.data(), n * sizeof(ngsld_item), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_std.p, std_rec, n * sizeof(ngsld_rec_std), hipMemcpyHostToDevice));
+  if (ext_rec != nullptr) HIP_TRY(c, hipMemcpy(d_ext.p, ext_rec, n * sizeof(ngsld_rec_ext), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_maf.p, maf.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), 2 * n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(d_meta.p, 0, 2 * sizeof(uint64_t)));
+  HIP_TRY(c, hipMemset(d_host.p, 0, sizeof(int)));
+  TextArgs t{};
+  t.items = d_items.p;
+  t.n_items = n;
+  t.out_base = 0;
+  t.n_pairs = n;
+  t.std_rec = d_std.p;
+  t.ext_rec = ext_rec != nullptr ? d_ext.p : nullptr;
+  t.maf = d_maf.p;
+  t.cum = d_cum.p;
+  t.infc = d_infc.p;
+  t.labels = nullptr;
+  t.label_off = nullptr;
+  t.lens = d_lens.p;
+  t.offs = d_offs.p;
+  t.text = d_text.p;
+  t.text_cap = text_cap;
+  t.overflow = d_meta.p + 1;
+  t.needs_host = d_host.p;
+  HIP_TRY(c, launch_text_lengths(t, c->stream));
+  HIP_TRY(c, text_scan(d_tmp.p, tmp_bytes, d_lens.p, d_offs.p, n, d_meta.p, c->stream));
+  if (text_cap > 0) HIP_TRY(c, launch_text_write(t, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint64_t meta[2];
+  int host = 0;
+  HIP_TRY(c, hipMemcpy(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(&host, d_host.p, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(row_len, d_lens.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *needs_host = host;
+  if (meta[0] > text_cap || meta[1] != 0)
+    return fail(c, NGSLD_ERR_INVALID, "ngsld_selftest_format: the rows take " + std::to_string(meta[0]) + " bytes, text_cap is " +
+                                          std::to_string(text_cap));
+  HIP_TRY(c, hipMemcpy(text, d_text.p, meta[0], hipMemcpyDeviceToHost));
+  return NGSLD_OK;
+} NGSLD_CATCH(c)
+
 uint64_t ngsld_slab_sites_for_budget(uint64_t n_ind, uint64_t budget_bytes) { return ngsld_sites_for_budget(n_ind, budget_bytes, 3); }
 
 uint64_t ngsld_sites_for_budget(uint64_t n_ind, uint64_t budget_bytes, int matrix_copies) {

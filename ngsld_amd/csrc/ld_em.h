@@ -406,6 +406,53 @@ __device__ __forceinline__ bool near_rounding(double v, double d) {
   return fabs((t - floor(t)) - 0.5) < d * 1e6;
 }
 
+// Is x closer than d to a point where the conversion to float rounds the other way?  (the midpoints between adjacent floats
+// are exact doubles: 25 significant bits)
+__device__ __forceinline__ bool near_float_midpoint(double x, double d) {
+  const float f = (float)x;
+  const double lo = 0.5 * ((double)f + (double)nextafterf(f, -__builtin_inff()));
+  const double hi = 0.5 * ((double)f + (double)nextafterf(f, __builtin_inff()));
+  return fabs(x - lo) <= d || fabs(x - hi) <= d;  // (NaN: false; +-inf: false)
+}
+
+// The float chi2 of the extended columns (ngsLD.cpp:328-333, ld_text.hip format_row) from hap values within dh of the
+// reference's: may the reference's chi2 print another sixth decimal?  A float rounding of the chain whose argument lies within
+// its error bound of a float midpoint may give the neighbouring float there.  A hap sum (freq_A, freq_B) that may round either
+// way changes every expected frequency: flagged.  A partial sum that may widens the bound on the reference's partial sum by a
+// float ulp; one that may not leaves the same float on both sides (bound 0).  Flagged when the final bound reaches a
+// sixth-decimal rounding point.  (Called genotypes put hap sums and partial sums exactly on float midpoints by the thousand.)
+__device__ __forceinline__ bool chi2_unsettled(double f0, double f1, double f2, double f3, double dh) {
+  const double sA = f0 + f1, sB = f0 + f2;
+  if (near_float_midpoint(sA, 2 * dh + 0x1p-53 * fabs(sA)) || near_float_midpoint(sB, 2 * dh + 0x1p-53 * fabs(sB))) return true;
+  const float freq_A = (float)sA, freq_B = (float)sB;
+  const float exp_hap[4] = {freq_A * freq_B, freq_A * (1 - freq_B), (1 - freq_A) * freq_B, (1 - freq_A) * (1 - freq_B)};
+  const double h[4] = {f0, f1, f2, f3};
+  float chi2 = 0;
+  double err = 0;  // |the reference's partial sum - chi2|
+  for (int i = 0; i < 4; i++) {
+    const double e = (double)exp_hap[i];
+    const double d = h[i] - e;
+    if (e == 0) {
+      if (fabs(h[i]) <= dh) return true;  // d * d / 0: inf here, NaN where the reference's hap is 0 (or the other way round)
+      return false;                       // inf from here on, on both sides
+    }
+    const double t = d * d / e;
+    const double s = (double)chi2 + t;
+    // the reference's term: d within dh + an ulp, then a square and a quotient, each rounded (generously: twice that)
+    const double dd = dh + 0x1p-52 * fabs(d);
+    const double ds = err + 2 * ((2 * fabs(d) * dd + dd * dd) / e + 0x1p-51 * t) + 0x1p-52 * fabs(s);
+    chi2 = (float)s;
+    if (near_float_midpoint(s, ds)) {
+      const double up = (double)nextafterf(chi2, __builtin_inff()) - (double)chi2;
+      const double dn = (double)chi2 - (double)nextafterf(chi2, -__builtin_inff());
+      err = ds + (up > dn ? up : dn);
+    } else {
+      err = 0;
+    }
+  }
+  return err > 0 && near_rounding((double)chi2, err);
+}
+
 // ngsLD.cpp:296-306 (hap-derived maf, D, D', r2) + pearson_r, one record per pair; pairs whose outcome the reference's
 // rounding decides are flagged for the exact-order replay (see kHapNoise / kReplayFloor above).
 __device__ __forceinline__ void write_pair(const PairArgs &A, uint64_t slot, double f0, double f1, double f2,
@@ -467,7 +514,8 @@ __device__ __forceinline__ void write_pair(const PairArgs &A, uint64_t slot, dou
            near_rounding(Dp, 2 * d_abs * (1.0 + fabs(Dp) * amp)) || near_rounding(o.r2, 2 * d_abs * (1.0 + o.r2 * amp));
     if (A.out_ext != nullptr)
       flag = flag || near_rounding(f0, d_abs) || near_rounding(f1, d_abs) || near_rounding(f2, d_abs) ||
-             near_rounding(f3, d_abs) || near_rounding(hm0, d_abs) || near_rounding(hm1, d_abs);
+             near_rounding(f3, d_abs) || near_rounding(hm0, d_abs) || near_rounding(hm1, d_abs) ||
+             (A.flag_text && chi2_unsettled(f0, f1, f2, f3, d_abs));
     if (flag) {
       atomicOr(&A.flags[flag_head_words(A.flag_cap) + (slot >> 5)], 1u << (slot & 31u));
       if (host_only && A.flags_host != nullptr) {

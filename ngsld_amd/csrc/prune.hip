@@ -239,6 +239,20 @@ bool lower_less(const std::string &x, const std::string &y) {  // Perl's lc(...)
   return x.size() < y.size();
 }
 
+// ngsld_selftest_printed: the quantiser of this file's edge_kernel and decay.hip's bin_kernel (ld_prune.h), value by value
+__global__ void printed_kernel(const double *x, uint64_t n, double min_weight, char type, double scale, int64_t *micro,
+                               int32_t *micro_ok, int64_t *label, int32_t *label_rc) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const double v = x[t];
+  int64_t q = 0, lab = 0;
+  const bool ok = ngsld::printed_micro(v, &q);  // (false for NaN / inf too; the bin kernel drops those before it quantises)
+  micro[t] = q;
+  micro_ok[t] = ok ? 1 : 0;
+  label_rc[t] = ngsld::prune_label(v, min_weight, type, scale, &lab);
+  label[t] = lab;
+}
+
 }  // namespace
 
 extern "C" {
@@ -557,6 +571,37 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     std::memcpy(stats, &S, std::min<size_t>(want, sizeof(S)));
     stats->struct_size = want;
   }
+  return NGSLD_OK;
+} NGSLD_CATCH(c)
+
+int ngsld_selftest_printed(ngsld_ctx *c, uint64_t n, const double *x, int32_t precision, int32_t weight_type, double min_weight,
+                           int64_t *micro, int32_t *micro_ok, int64_t *label, int32_t *label_rc) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  if (n == 0 || n > (1ull << 26) || x == nullptr || micro == nullptr || micro_ok == nullptr || label == nullptr ||
+      label_rc == nullptr)
+    return fail(c, NGSLD_ERR_INVALID, "ngsld_selftest_printed: 1 <= n <= 2^26 values and every pointer set");
+  if (precision < 0 || precision > 15) return fail(c, NGSLD_ERR_INVALID, "prune precision must be in [0, 15]");
+  if (weight_type != 'a' && weight_type != 'e' && weight_type != 'n')
+    return fail(c, NGSLD_ERR_INVALID, "prune weight type must be 'a', 'e' or 'n'");
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  DevBuf<double> d_x;
+  DevBuf<int64_t> d_micro, d_label;
+  DevBuf<int32_t> d_ok, d_rc;
+  HIP_TRY(c, d_x.resize(n));
+  HIP_TRY(c, d_micro.resize(n));
+  HIP_TRY(c, d_label.resize(n));
+  HIP_TRY(c, d_ok.resize(n));
+  HIP_TRY(c, d_rc.resize(n));
+  HIP_TRY(c, hipMemcpy(d_x.p, x, n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(printed_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, d_x.p, n, min_weight, (char)weight_type,
+                     ngsld::prune_scale(precision), d_micro.p, d_ok.p, d_label.p, d_rc.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(micro, d_micro.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(micro_ok, d_ok.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(label, d_label.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(label_rc, d_rc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return NGSLD_OK;
 } NGSLD_CATCH(c)
 

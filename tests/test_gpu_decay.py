@@ -74,6 +74,10 @@ CASES = {
     "bin_62.5": (400, 64, {}, 1, WIN, dict(bin_size=62.5, ld=("D", "r2")), None),
     "bin_1000": (400, 64, {}, 1, WIN, dict(bin_size=1000), None),
     "bin_250_kb_limit": (400, 64, {}, 1, WIN, dict(bin_size=250, max_kb_dist=7.5), None),
+    # bin sizes that are not dyadic: k * B is rounded, bin_of's corrections and the %.15g break labels come into play
+    "bin_33.3": (400, 64, {}, 1, WIN, dict(bin_size=33.3, ld=ALL4), None),
+    "bin_1.1": (300, 64, {}, 1, dict(max_kb_dist=3, extend_out=True), dict(bin_size=1.1), None),
+    "bin_7.3": (400, 8, {}, 1, WIN, dict(bin_size=7.3, ld=("D", "r2")), None),
 }
 
 
@@ -99,6 +103,21 @@ def test_limit_on_a_present_dist():
     finally:
         eng.close()
     assert f"\t{int(d)}\t" in text  # (the limit is a dist of the table)
+
+
+@pytest.mark.parametrize("bin_size", [33.3, 7.3, 1.1])
+def test_dist_on_an_inexact_break(bin_size):
+    """Sites at every position 1..400: every integer dist is in the table, among them breaks k * B that round to an integer
+    (10 * 33.3 == 333.0), where d / B lands a hair above k and only the right-closed rule puts the row in bin k - 1."""
+    n = 400
+    raw = synth.make_gl_numpy(n, 16, 23, depth=4.0)
+    chrs, pos = ["chr1"] * n, np.arange(1, n + 1)
+    on_break = [k * bin_size for k in range(1, int(n / bin_size) + 1) if k * bin_size == int(k * bin_size)]
+    assert on_break
+    _, _, want = _case(raw, chrs, pos, dict(extend_out=True, max_kb_dist=0), dict(bin_size=bin_size, ld=ALL4))
+    labels = [w[0] for w in want]
+    assert all(float(f"{b:.15g}") in labels for b in on_break if b < n - 1)
+    print(f"bin {bin_size}: {len(want)} bins, dists on the breaks {on_break[:4]}")
 
 
 def _knob_case(monkeypatch, env):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from ngsld_amd import capi, shard
+import printed_values
 from util import Fixture, fixtures
 
 POS_FIXTURES = [n for n in fixtures() if Fixture(n).has_pos]
@@ -113,16 +114,7 @@ def test_formatter_nan_inf_and_null_labels():
 def test_format_double_is_printf_exact():
     """The fast %f / %.0f path against the C library's exact conversion (Python's % formatting is correctly
     rounded on the exact binary value, like glibc), over magnitudes, ties, subnormals and non-finite values."""
-    import struct
-    rng = np.random.default_rng(11)
-    vals = [0.0, -0.0, 1.0, -1.0, 0.5, 0.0078125, 0.00390625, 2.5e-7, 5e-7, 4.9999999999999998e-7, 1.5e-6, 0.1, 0.7,
-            1e-300, 5e-324, 123456789.987654321, 9.2e12, 9.3e12, 1e15, 2.0 ** 53, 2.0 ** 63, 1e22, 1e300,
-            999999.9999995, 0.9999995, 0.9999994999999999, 1 - 2.0 ** -53]
-    vals += list(rng.random(60000))                                        # [0,1): the bulk of what is printed
-    vals += list((rng.random(60000) - 0.5) * 10.0 ** rng.integers(-12, 14, 60000))
-    vals += [struct.unpack("<d", struct.pack("<Q", int(b)))[0] for b in rng.integers(0, 2 ** 63, 40000)]
-    # exact ties at the 6th decimal: k / 2^j with 7+ decimals
-    vals += [float(k) / 2.0 ** j for j in range(7, 20) for k in range(1, 200, 2)]
+    vals = printed_values.host_format_values()
     for v in vals:
         if np.isnan(v):
             continue
