@@ -478,6 +478,50 @@ int ngsld_decay(ngsld_ctx *ctx, const ngsld_decay_params *params, ngsld_decay_st
  * NULL; *n_bins (may be NULL) receives the number of bins. */
 int ngsld_decay_bins(ngsld_ctx *ctx, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins);
 
+/* ---- LD blocks on the device (BLOCKS.md) ----------------------------------------------------------------------------------
+ * The square matrices the reference's scripts/LD_blocks.sh hands to LDheatmap for one region CHR:START-END, for the TSV this
+ * context's plan would print -- without the TSV: only the rows of the region's sites run again (chunk by chunk into device
+ * records, every pair kernel and the exact-order replay included), a kernel scatters their pairs into dense matrices and a
+ * formatter writes them as text.  A site is a member iff its label (up to the first TAB) is CHR ":" p with START <= p <= END;
+ * the matrix holds the members that are one end of an in-region pair, ordered by p.  Cell [a][b] is the pair (a, b) with a
+ * the earlier site of the file, NA elsewhere (the diagonal included); a cell's text is what the TSV prints for that pair.
+ * Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_blocks_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (the script's pair: 4 | 8) */
+  const char *chr;            /* CHR */
+  uint64_t start, end;        /* START < END, both inclusive */
+} ngsld_blocks_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_blocks_stats) */
+  uint32_t reserved;
+  uint64_t members, sites;    /* region members; matrix sites (members that are one end of an in-region pair) */
+  uint64_t pairs, pairs_in_region;  /* pairs computed (the members' rows only); of them in the region */
+  uint64_t cells_na, host_rows, chunks;  /* NA cells of a matrix; text rows formatted on the host; chunks of rows the pairs
+                                            ran in */
+  double pairs_ms, scatter_ms, format_ms, total_ms;  /* pair kernels + replay, the scatter and site kernels (kernel time),
+                                                 text (ngsld_blocks_text), the whole ngsld_blocks call */
+} ngsld_blocks_stats;
+
+/* Block matrices after ngsld_plan; the context keeps them until the next ngsld_blocks, ngsld_plan or ngsld_set_*.  labels =
+ * n_sites C strings, the TSV's first two columns (NULL or "(null)" labels: NGSLD_ERR_INVALID, blocks need positions).  No
+ * in-region pair: NGSLD_OK with sites == 0.  NGSLD_ERR_UNSUPPORTED, naming the label, for a site of CHR whose position is not
+ * plain decimal digits or two members at one position; also for more than 2^15 members or matrices the device has no room
+ * for (fields x members^2 x 8 + members^2 bytes).  stats may be NULL. */
+int ngsld_blocks(ngsld_ctx *ctx, const ngsld_blocks_params *params, const char *const *labels, ngsld_blocks_stats *stats);
+/* The matrix sites of the last ngsld_blocks in matrix order (increasing position): up to cap site indices into site[];
+ * *n_sites (may be NULL) receives their number. */
+int ngsld_blocks_sites(ngsld_ctx *ctx, uint64_t cap, uint64_t *site, uint64_t *n_sites);
+/* One chosen statistic's matrix (field = TSV column 4..7), sites x sites in matrix order, row-major: values[] the records'
+ * doubles (NaN where no pair is), present[] 1 where a pair is; either pointer may be NULL. */
+int ngsld_blocks_matrix(ngsld_ctx *ctx, int field, double *values, uint8_t *present);
+/* One chosen statistic's matrix as a file (BLOCKS.md: a label row, then a label and sites cells per row), handed to sink in
+ * order, in chunks; a sink that returns non-zero stops it (NGSLD_ERR_SINK).  stats (may be NULL): the call's format_ms (its
+ * time outside the sink) and host_rows are added to it. */
+typedef int (*ngsld_text_fn)(void *user, const char *text, uint64_t len);
+int ngsld_blocks_text(ngsld_ctx *ctx, int field, ngsld_text_fn sink, void *user, ngsld_blocks_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,7 @@ SYMBOLS = [
     "ngsld_host_gz_open", "ngsld_host_gz_close",
     "ngsld_prune", "ngsld_host_prune_graph", "ngsld_host_prune_label",
     "ngsld_decay", "ngsld_decay_bins", "ngsld_host_decay_fit",
+    "ngsld_blocks", "ngsld_blocks_sites", "ngsld_blocks_matrix", "ngsld_blocks_text",
 ]
 
 
@@ -132,6 +133,23 @@ class DecayStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
                 ("bins", C.c_uint64), ("bin_slots", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double),
                 ("bin_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class BlocksParams(C.Structure):
+    """ngsld_blocks_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("chr", C.c_char_p), ("start", C.c_uint64),
+                ("end", C.c_uint64)]
+
+
+class BlocksStats(C.Structure):
+    """ngsld_blocks_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("members", C.c_uint64), ("sites", C.c_uint64),
+                ("pairs", C.c_uint64), ("pairs_in_region", C.c_uint64), ("cells_na", C.c_uint64), ("host_rows", C.c_uint64),
+                ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("scatter_ms", C.c_double), ("format_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 
 class DecayFitResult(C.Structure):
@@ -260,6 +278,11 @@ def lib() -> C.CDLL:
             L.ngsld_decay.argtypes = [vp, C.POINTER(DecayParams), C.POINTER(DecayStats)]
             L.ngsld_decay_bins.argtypes = [vp, u64, vp, vp, vp, C.POINTER(u64)]
             L.ngsld_host_decay_fit.argtypes = [u64, vp, vp, C.c_int, dbl, dbl, C.POINTER(DecayFitResult)]
+        if hasattr(L, "ngsld_blocks"):
+            L.ngsld_blocks.argtypes = [vp, C.POINTER(BlocksParams), C.POINTER(C.c_char_p), C.POINTER(BlocksStats)]
+            L.ngsld_blocks_sites.argtypes = [vp, u64, vp, C.POINTER(u64)]
+            L.ngsld_blocks_matrix.argtypes = [vp, C.c_int, vp, vp]
+            L.ngsld_blocks_text.argtypes = [vp, C.c_int, TEXT_FN, vp, C.POINTER(BlocksStats)]
         _lib = L
     return _lib
 
@@ -1003,3 +1026,51 @@ class Engine:
         for k, f in enumerate(names):
             bins[f] = mean[:nb, k].copy()
         return bins, {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}
+
+    def blocks(self, labels: list[str], chr: str, start: int, end: int,
+               ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:
+        """LD block matrices of one region on the device (ngsld_blocks, BLOCKS.md): (sites, {stat: (values, present)}, stats).
+        sites are the matrix sites' indices in matrix order; values[a, b] is the record's double of the pair (a, b) (NaN where
+        present[a, b] is 0); stats are r2_ExpG, D, Dp, r2.  blocks_text(stat) then gives the matrix as a file."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        arr = (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels]) if labels is not None else None
+        p = BlocksParams(C.sizeof(BlocksParams), mask, chr.encode(), int(start), int(end))
+        st = BlocksStats()
+        st.struct_size = C.sizeof(BlocksStats)
+        self._check(self._L.ngsld_blocks(self._h, C.byref(p), arr, C.byref(st)))
+        m = st.sites
+        sites = np.zeros(max(m, 1), dtype=np.uint64)
+        got = C.c_uint64()
+        self._check(self._L.ngsld_blocks_sites(self._h, m, sites.ctypes.data, C.byref(got)))
+        assert got.value == m
+        mats = {}
+        for k, f in enumerate(DECAY_FIELDS):
+            if not (mask >> k) & 1:
+                continue
+            values = np.zeros((m, m))
+            present = np.zeros((m, m), dtype=np.uint8)
+            if m:
+                self._check(self._L.ngsld_blocks_matrix(self._h, 4 + k, values.ctypes.data, present.ctypes.data))
+            mats[f] = (values, present)
+        return sites[:m].astype(np.int64), mats, {k: getattr(st, k) for k, _ in BlocksStats._fields_
+                                                  if k not in ("struct_size", "reserved")}
+
+    def blocks_text(self, field: str, stats: dict | None = None) -> bytes:
+        """One statistic's matrix of the last blocks() as a file (ngsld_blocks_text).  stats (optional dict): gets the call's
+        format_ms, host_rows and the number of pieces the sink received ("pieces")."""
+        parts = []
+
+        def sink(_user, text, n):
+            parts.append(C.string_at(text, n))
+            return 0
+
+        st = BlocksStats()
+        st.struct_size = C.sizeof(BlocksStats)
+        self._check(self._L.ngsld_blocks_text(self._h, 4 + DECAY_FIELDS.index(field), TEXT_FN(sink), None, C.byref(st)))
+        if stats is not None:
+            stats.update(format_ms=st.format_ms, host_rows=st.host_rows, pieces=len(parts))
+        return b"".join(parts)

@@ -13,6 +13,9 @@
 //     getopt runs, so the reference's flags keep every abbreviation and message they have;
 //   * --decay_out FILE / --decay_fit FILE (new) and the other --decay_* flags: the distance bins and the decay fit of
 //     scripts/fit_LDdecay.R, binned on the device (ngsld_decay, DECAY.md); taken out of argv the same way, no TSV without --out;
+//   * --blocks_out PREFIX (new) and the other --blocks_* flags: the r2 / D' matrices of one region that scripts/LD_blocks.sh
+//     hands to LDheatmap, built on the device (ngsld_blocks, BLOCKS.md) and written as PREFIX.<stat>.tsv; taken out of argv
+//     the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -184,6 +187,19 @@ void take_decay_args(int *argc, char **argv, DecayArgs *da) {
   take_flags(argc, argv, "decay_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &da->given);
 }
 
+// ---- --blocks_* (new): LD block matrices of one region on the device ----
+struct BlocksArgs {
+  bool given = false;  // any --blocks_* flag
+  const char *out = nullptr, *chr = nullptr, *start = nullptr, *end = nullptr, *ld = nullptr;
+  ngsld_blocks_params p{};
+};
+
+void take_blocks_args(int *argc, char **argv, BlocksArgs *ba) {
+  static const char *const kValued[] = {"blocks_out", "blocks_chr", "blocks_start", "blocks_end", "blocks_ld"};
+  const char **const dst[] = {&ba->out, &ba->chr, &ba->start, &ba->end, &ba->ld};
+  take_flags(argc, argv, "blocks_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &ba->given);
+}
+
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
   if (txt == nullptr || *txt == 0) return false;
@@ -289,6 +305,53 @@ void check_decay_args(const Params &pars, DecayArgs *da) {
   if (pars.devices.size() > 1) error(__FUNCTION__, "--decay_out runs on one device: it cannot be combined with --devices!");
 }
 
+// a --blocks_start / --blocks_end value: plain decimal digits
+bool parse_position(const char *txt, uint64_t *out) {
+  if (txt == nullptr || *txt == 0 || std::strlen(txt) > 19) return false;
+  for (const char *q = txt; *q; ++q)
+    if (*q < '0' || *q > '9') return false;
+  *out = std::strtoull(txt, nullptr, 10);
+  return true;
+}
+
+// the statistics of a comma-separated list (--decay_ld, --blocks_ld) as a mask, bit k = column 4 + k; 0 when a name is unknown
+uint32_t parse_ld_list(const char *txt) {
+  uint32_t fields = 0;
+  const std::string s = txt;
+  size_t b = 0;
+  while (true) {
+    const size_t e = std::min(s.find(',', b), s.size());
+    const std::string name = s.substr(b, e - b);
+    int f = -1;
+    for (int k = 0; k < 4; ++k)
+      if (name == kDecayFields[k]) f = k;
+    if (f < 0) return 0;
+    fields |= 1u << f;
+    if (e == s.size()) return fields;
+    b = e + 1;
+  }
+}
+
+void check_blocks_args(const Params &pars, BlocksArgs *ba) {
+  if (!ba->given) return;
+  if (ba->out == nullptr) error(__FUNCTION__, "the --blocks_* options need --blocks_out PREFIX!");
+  if (*ba->out == 0) error(__FUNCTION__, "--blocks_out needs a file name prefix!");
+  ngsld_blocks_params &p = ba->p;
+  p.struct_size = sizeof(p);
+  p.fields = 4u | 8u;  // Dp, r2: the script's pair
+  if (ba->chr == nullptr || *ba->chr == 0) error(__FUNCTION__, "--blocks_out needs the region's chromosome: --blocks_chr CHR!");
+  p.chr = ba->chr;
+  if (ba->start == nullptr) error(__FUNCTION__, "--blocks_out needs the region's start: --blocks_start INT!");
+  if (ba->end == nullptr) error(__FUNCTION__, "--blocks_out needs the region's end: --blocks_end INT!");
+  if (!parse_position(ba->start, &p.start)) error(__FUNCTION__, "--blocks_start must be a non-negative integer!");
+  if (!parse_position(ba->end, &p.end)) error(__FUNCTION__, "--blocks_end must be a non-negative integer!");
+  if (p.start >= p.end) error(__FUNCTION__, "start position must be smaller than end position.");
+  if (ba->ld && (p.fields = parse_ld_list(ba->ld)) == 0)
+    error(__FUNCTION__, "--blocks_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+  if (pars.in_pos == nullptr) error(__FUNCTION__, "--blocks_out needs positions: it cannot run without --pos!");
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--blocks_out runs on one device: it cannot be combined with --devices!");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -346,6 +409,30 @@ void run_decay(ngsld_ctx *ctx, const Params &pars, DecayArgs &da) {
   if (pars.verbose >= 1)
     fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)st.pairs_counted,
             (unsigned long)st.pairs);
+}
+
+int write_blocks_text(void *user, const char *text, uint64_t len) {
+  return fwrite(text, 1, len, static_cast<FILE *>(user)) == len ? 0 : 1;
+}
+
+void run_blocks(ngsld_ctx *ctx, const Params &pars, BlocksArgs &ba, const ngsld_pos *pos) {
+  std::vector<const char *> lab(pars.n_sites);
+  for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  ngsld_blocks_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_blocks(ctx, &ba.p, lab.data(), &st) != NGSLD_OK) error("ngsld_blocks", ngsld_last_error(ctx));
+  if (st.sites == 0) error(__FUNCTION__, "no SNPs found in region.");
+  for (int k = 0; k < 4; ++k) {
+    if (!((ba.p.fields >> k) & 1u)) continue;
+    const std::string path = std::string(ba.out) + "." + kDecayFields[k] + ".tsv";
+    FILE *f = fopen(path.c_str(), "w");
+    if (f == nullptr) error(__FUNCTION__, "cannot open LD blocks output file!");
+    const int rc = ngsld_blocks_text(ctx, 4 + k, write_blocks_text, f, &st);
+    if (rc == NGSLD_ERR_SINK || fclose(f) != 0) error(__FUNCTION__, "cannot write LD blocks output file!");
+    if (rc != NGSLD_OK) error("ngsld_blocks_text", ngsld_last_error(ctx));
+  }
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD blocks: %lu sites, %lu pairs in region\n", (unsigned long)st.sites, (unsigned long)st.pairs_in_region);
 }
 
 // labels one per line, in site order; a name ending in .gz is written gzip-compressed
@@ -810,10 +897,14 @@ int main(int argc, char **argv) {
   take_prune_args(&argc, argv, &prune);
   DecayArgs decay;
   take_decay_args(&argc, argv, &decay);
+  BlocksArgs blocks;
+  take_blocks_args(&argc, argv, &blocks);
   parse_cmd_args(&pars, argc, argv);
   check_prune_args(pars, &prune);
   check_decay_args(pars, &decay);
-  const bool write_tsv = !(prune.given || decay.given) || pars.out != NULL;  // --prune_out / --decay_out without --out: no TSV
+  check_blocks_args(pars, &blocks);
+  // --prune_out / --decay_out / --blocks_out without --out: no TSV
+  const bool write_tsv = !(prune.given || decay.given || blocks.given) || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -954,6 +1045,8 @@ int main(int argc, char **argv) {
     error(__FUNCTION__, "--prune_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0 && decay.given)
     error(__FUNCTION__, "--decay_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  if (slab_sites > 0 && blocks.given)
+    error(__FUNCTION__, "--blocks_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -1099,6 +1192,10 @@ int main(int argc, char **argv) {
   if (decay.given) {  // (a pass of the pair kernels of its own)
     run_decay(ctx, pars, decay);
     timing_report.mark("LD decay");
+  }
+  if (blocks.given) {  // (a pass of the pair kernels over the region's rows)
+    run_blocks(ctx, pars, blocks, pos);
+    timing_report.mark("LD blocks");
   }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)

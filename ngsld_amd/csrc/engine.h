@@ -445,6 +445,29 @@ struct ngsld_ctx {
   uint32_t decay_fields = 0;
   std::vector<double> decay_dist, decay_mean;  // decay_mean: [bin][field], fields in TSV column order
   std::vector<uint64_t> decay_count;
+
+  // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
+  // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
+  uint32_t blocks_fields = 0;
+  uint64_t blocks_members = 0;
+  DevBuf<double> d_blocks_val;                // [field rank][members][members], written only where present
+  DevBuf<uint8_t> d_blocks_present;           // [members][members]
+  DevBuf<uint32_t> d_blocks_col;              // [sites] member index of each matrix site, in matrix order
+  std::vector<uint64_t> blocks_site;          // [sites] site index of each matrix site
+  std::vector<std::string> blocks_label;      // [sites] its label up to the first TAB
+  DevBuf<char> d_blocks_label;                // ... back to back, for the text rows
+  DevBuf<uint64_t> d_blocks_label_off;        // [sites + 1]
+  void clear_blocks() {
+    blocks_fields = 0;
+    blocks_members = 0;
+    d_blocks_val.release();
+    d_blocks_present.release();
+    d_blocks_col.release();
+    d_blocks_label.release();
+    d_blocks_label_off.release();
+    blocks_site.clear();
+    blocks_label.clear();
+  }
 };
 
 namespace ngsld {
@@ -513,12 +536,14 @@ hipError_t timed_launch(ngsld_ctx *c, const PairArgs &a, hipStream_t stream);
 PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext,
                    uint32_t *d_flags = nullptr, uint32_t flag_cap = 0, uint64_t flag_n = 0);
 
-// Rows [0, n_sites) chunk by chunk into d_rec (room for rec_cap records): chunks of up to chunk_pairs records, a longer row
-// is a chunk of its own (NGSLD_ERR_UNSUPPORTED past rec_cap): ngsld_run_device + ngsld_finish_device on the context's stream, so every record is final (replayed pairs
-// carry their replayed values), then on_chunk(r0, r1, pairs) for the chunk's rows [r0, r1).  *pairs_ms adds the wall time of
-// the pair phase.  ngsld_prune and ngsld_decay read the records this way.
+// Rows [row_begin, row_end) (default: all of them) chunk by chunk into d_rec (room for rec_cap records): chunks of up to
+// chunk_pairs records, a longer row is a chunk of its own (NGSLD_ERR_UNSUPPORTED past rec_cap): ngsld_run_device +
+// ngsld_finish_device on the context's stream, so every record is final (replayed pairs carry their replayed values), then
+// on_chunk(r0, r1, pairs) for the chunk's rows [r0, r1).  *pairs_ms adds the wall time of the pair phase.  ngsld_prune and
+// ngsld_decay read the records of every row this way, ngsld_blocks those of the region's rows.
 int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
-                      const std::function<int(uint64_t r0, uint64_t r1, uint64_t pairs)> &on_chunk);
+                      const std::function<int(uint64_t r0, uint64_t r1, uint64_t pairs)> &on_chunk, uint64_t row_begin = 0,
+                      uint64_t row_end = UINT64_MAX);
 
 // ---- engine_replay.hip ----
 // send_flag_rows: for the pairs a text batch leaves to the host (its flag list, or its host-only list behind a device-side

@@ -32,6 +32,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
   stop_exact_store(c);  // (the builder of the last matrix' exact store, if it is still at it)
   c->have_geno = false;
   c->planned = false;
+  c->clear_blocks();
   c->text_mode = false;  // labels belong to a matrix
   c->replay_read = nullptr;  // and so does the replay source
   c->replay_user = nullptr;
@@ -230,7 +231,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
 
 extern "C" {
 
-const char *ngsld_version(void) { return "ngsld-amd 0.7.0 (gfx950; reference ngsLD 1.2.1)"; }
+const char *ngsld_version(void) { return "ngsld-amd 0.8.0 (gfx950; reference ngsLD 1.2.1)"; }
 
 int ngsld_create(int device, ngsld_ctx **out) {
   if (out == nullptr) return NGSLD_ERR_INVALID;
@@ -371,6 +372,7 @@ int ngsld_set_pos_dist(ngsld_ctx *c, const double *pos_dist) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   if (!c->have_geno) return fail(c, NGSLD_ERR_INVALID, "set the genotype data before the positions");
   c->planned = false;
+  c->clear_blocks();
   if (pos_dist == nullptr)
     c->h_pos_dist.assign(c->n_sites, std::numeric_limits<double>::infinity());  // ngsLD.cpp:134
   else
@@ -415,6 +417,7 @@ int ngsld_describe_dispatch(uint64_t n_ind, int ignore_miss_data, char *buf, siz
 
 int ngsld_set_tuning(ngsld_ctx *c, uint32_t pairs_per_item, uint64_t batch_pairs) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
+  c->clear_blocks();
   if (pairs_per_item) {
     c->pairs_per_item = pairs_per_item;
     c->planned = false;

@@ -968,6 +968,7 @@ int ngsld_set_replay_source(ngsld_ctx *c, ngsld_read_sites_fn read, void *user) 
   c->replay_read = read;
   c->replay_user = user;
   c->planned = false;  // a --min_maf tie is settled at plan time
+  c->clear_blocks();
   return NGSLD_OK;
 }
 
@@ -978,6 +979,7 @@ int ngsld_set_replay_matrix(ngsld_ctx *c, const double *values) {
   c->replay_matrix = values;
   c->replay_read = nullptr;
   c->replay_user = nullptr;
+  c->clear_blocks();
   c->planned = false;  // a --min_maf tie is settled at plan time
   return NGSLD_OK;
 }
@@ -986,12 +988,14 @@ int ngsld_set_replay(ngsld_ctx *c, int enable) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   c->replay_on = enable != 0;
   c->planned = false;
+  c->clear_blocks();
   return NGSLD_OK;
 }
 
 int ngsld_set_exact_store(ngsld_ctx *c, int mode) {
   if (c == nullptr || mode < 0 || mode > 2) return NGSLD_ERR_INVALID;
   c->exact_mode = mode;
+  c->clear_blocks();
   return NGSLD_OK;
 }
 

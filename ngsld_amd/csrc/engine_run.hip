@@ -76,6 +76,7 @@ int ngsld_set_text_output(ngsld_ctx *c, const char *const *labels, int enable) t
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // (a failure some earlier call already reported must not surface as a launch's "last error")
   c->text_mode = false;
+  c->clear_blocks();
   if (!enable) return NGSLD_OK;
   c->have_labels = labels != nullptr;
   c->max_label = 6;
@@ -1031,8 +1032,8 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
 }
 
 int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
-                      const std::function<int(uint64_t, uint64_t, uint64_t)> &on_chunk) {
-  const uint64_t n = c->n_sites;
+                      const std::function<int(uint64_t, uint64_t, uint64_t)> &on_chunk, uint64_t row_begin, uint64_t row_end) {
+  const uint64_t n = std::min<uint64_t>(row_end, c->n_sites);
   // The records are read as printed (ld_prune.h): the launches flag, and the replay settles, the pairs whose sixth decimal
   // or sign rounding noise could change, as for text output -- a D one ulp off an odd / 128 tie would quantise to the other
   // neighbour than the reference's "%f"
@@ -1041,7 +1042,7 @@ int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, 
     ~FlagText() { c->dev_run_flag_text = false; }
   } flag_text{c};
   c->dev_run_flag_text = true;
-  for (uint64_t r0 = 0; r0 < n;) {
+  for (uint64_t r0 = row_begin; r0 < n;) {
     uint64_t r1 = r0 + 1;
     while (r1 < n && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
     const uint64_t np = c->h_row_off[r1] - c->h_row_off[r0];
