@@ -3,11 +3,11 @@
 // they are copied out or written as text.  BLOCKS.md has the rule, the deviations and why a cell's text is the TSV's.
 //
 //   members  host: each label's CHR:pos (up to the first TAB), the region's sites, their order by position (ord, -1 elsewhere)
-//   pairs    run_record_chunks over each maximal run of member rows (an in-region pair has a member as s1): replayed pairs
-//            carry their replayed values, the rows of other sites are not run
-//   scatter  one wavefront per work item, one lane per candidate (ld_text.hip's mapping): the record's double bits of every
-//            chosen field to M_f[ord(s1) * n + ord(s2)], a presence byte to P[...] -- pairs are unique, no atomics; in file
-//            order = position order the lanes of an item write consecutive columns of one row
+//   pairs    run_record_chunks over the member rows (an in-region pair has a member as s1): replayed pairs carry their
+//            replayed values, the rows of other sites are not run
+//   scatter  one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the record's
+//            double bits of every chosen field to M_f[ord(s1) * n + ord(s2)], a presence byte to P[...] -- pairs are unique,
+//            no atomics; in file order = position order the lanes of an item write consecutive columns of one row
 //   sites    members with a pair in their row or column: one pass over P (lanes over columns), compacted by hipCUB
 //   text     ngsld_blocks_text: the lengths (one wavefront per matrix row, lanes over columns, a cross-lane sum), an exclusive
 //            scan over the rows (text_scan), then the rows in chunks sized to a pinned buffer, each cell at its offset from a
@@ -18,11 +18,10 @@
 #include "../../include/ngsld_host.h"
 #include "engine.h"
 #include "ld_fmt.h"
+#include "ld_records.h"
 
 namespace {
 
-// records of one chunk of rows (32 B each)
-constexpr uint64_t kChunkPairs = 1ull << 24;
 // members beyond this are refused: an LDheatmap region is hundreds to a few thousand sites
 constexpr uint64_t kMaxMembers = 1ull << 15;
 // text of one chunk of rows (pinned); a longer row is a chunk of its own
@@ -56,8 +55,8 @@ __global__ __launch_bounds__(256) void scatter_kernel(ScatterArgs A) {
     if (c < it.count && ((it.mask >> c) & 1ull)) {
       const int32_t o1 = A.ord[it.s1], o2 = A.ord[it.s2_begin + c];
       if (o1 >= 0 && o2 >= 0) {
-        const uint64_t k = it.first_record - A.out_base + (uint64_t)__popcll(it.mask & ((1ull << c) - 1ull));
-        const unsigned long long *r = reinterpret_cast<const unsigned long long *>(A.rec + k);  // (bits: NaN signs survive)
+        // (the record's bits, a field's at its index in ngsld_rec_std: NaN signs survive)
+        const unsigned long long *r = reinterpret_cast<const unsigned long long *>(A.rec + record_of(it, c, A.out_base));
         const uint64_t cell = (uint64_t)o1 * A.n + (uint64_t)o2;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
@@ -187,12 +186,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t *P, const uns
   }
 }
 
-inline unsigned blocks_for(uint64_t threads, unsigned per_block = 256) { return (unsigned)((threads + per_block - 1) / per_block); }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the label's part up to its first TAB (a pos file with extra columns puts them behind one)
 std::string label_key(const char *l) {
   const char *t = std::strchr(l, '\t');
@@ -214,9 +207,7 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   const auto t_all = std::chrono::steady_clock::now();
   c->clear_blocks();
   if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (p == nullptr || p->struct_size != sizeof(ngsld_blocks_params))
-    return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks_params: struct_size must be sizeof(ngsld_blocks_params)");
-  if (stats != nullptr && stats->struct_size < sizeof(uint32_t)) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks_stats: struct_size not set");
+  if (const int rc = check_struct_sizes(c, p, "ngsld_blocks_params", stats, "ngsld_blocks_stats")) return rc;
   if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "blocks fields must be a non-empty mask of 1, 2, 4, 8");
   if (p->chr == nullptr) return fail(c, NGSLD_ERR_INVALID, "blocks chr is NULL");
   if (!(p->start < p->end)) return fail(c, NGSLD_ERR_INVALID, "start position must be smaller than end position.");
@@ -228,9 +219,8 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   std::memset(&S, 0, sizeof(S));
   S.struct_size = sizeof(S);
   hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0}, ns = 0;
-  for (int f = 0; f < 4; ++f)
-    if ((p->fields >> f) & 1u) field[ns++] = f;
+  int field[4] = {0, 0, 0, 0};
+  const int ns = field_list(p->fields, field);
 
   // ---- members: CHR:p with START <= p <= END, in position order ----
   const std::string chr = p->chr;
@@ -283,25 +273,12 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, c->d_blocks_present.resize((size_t)n * n));
     HIP_TRY(c, hipMemsetAsync(c->d_blocks_present.p, 0, n * n, st));
     HIP_TRY(c, hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
-    uint64_t chunk = kChunkPairs;
-    if (const char *e = test_knob("BLOCKS_CHUNK_PAIRS")) chunk = std::max<uint64_t>(1, std::min<uint64_t>(kChunkPairs, std::strtoull(e, nullptr, 10)));
-    // records: the chunk, or the longest member row when one is longer (a row is never cut)
-    uint64_t longest = 0;
-    for (uint64_t s = 0; s < n_sites; ++s)
-      if (is_member[s]) longest = std::max<uint64_t>(longest, c->h_row_off[s + 1] - c->h_row_off[s]);
-    const uint64_t rec_cap = std::max<uint64_t>(std::min<uint64_t>(S.pairs, chunk), longest);
+    const uint64_t chunk = record_chunk(test_knob("BLOCKS_CHUNK_PAIRS"));
+    const uint64_t rec_cap = record_cap(c, chunk, is_member.data());
     DevBuf<ngsld_rec_std> d_rec;
     HIP_TRY(c, d_rec.resize(rec_cap));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(c, hipEventCreate(&ev0));
-    HIP_TRY(c, hipEventCreate(&ev1));
-    struct Events {
-      hipEvent_t a, b;
-      ~Events() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-      }
-    } events_{ev0, ev1};
+    EventPair ev;
+    HIP_TRY(c, ev.create());
     ScatterArgs A{};
     A.rec = d_rec.p;
     A.ord = d_ord.p;
@@ -312,37 +289,17 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     A.present = c->d_blocks_present.p;
     A.in_region = d_count.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    auto on_chunk = [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
+    // the member rows only: the rows of other sites are not run
+    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
       A.out_base = c->h_row_off[r0];
-      const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-      HIP_TRY(c, hipEventRecord(ev0, st));
-      const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
-      for (uint64_t off = i0; off < i1; off += max_items) {
-        A.items = c->d_items.p + off;
-        A.n_items = std::min<uint64_t>(max_items, i1 - off);
-        hipLaunchKernelGGL(scatter_kernel, dim3(std::min<unsigned>(blocks_for(A.n_items * 64), max_blocks)), dim3(256), 0, st, A);
-        HIP_TRY(c, hipGetLastError());
-      }
-      HIP_TRY(c, hipEventRecord(ev1, st));
-      HIP_TRY(c, hipEventSynchronize(ev1));  // (the next chunk's pairs overwrite the records)
-      float ms = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
-      S.scatter_ms += ms;
-      ++S.chunks;
-      return NGSLD_OK;
-    };
-    // each maximal run of member rows: non-member rows between two runs are not run
-    for (uint64_t s = 0; s < n_sites;) {
-      if (!is_member[s]) {
-        ++s;
-        continue;
-      }
-      uint64_t e = s + 1;
-      while (e < n_sites && is_member[e]) ++e;
-      const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, on_chunk, s, e);
-      if (rc != NGSLD_OK) return rc;
-      s = e;
-    }
+      // (it returns once the launches are done: the next chunk's pairs overwrite the records)
+      return launch_record_items(c, ev, r0, r1, &S.scatter_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
+        A.items = items;
+        A.n_items = n_items;
+        hipLaunchKernelGGL(scatter_kernel, dim3(std::min<unsigned>(blocks_for(n_items * 64), max_blocks)), dim3(256), 0, st, A);
+      });
+    }, is_member.data());
+    if (rc != NGSLD_OK) return rc;
 
     // ---- matrix sites: members with a pair in their row or column, compacted in matrix order ----
     DevBuf<uint8_t> d_mark;
@@ -351,7 +308,7 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, d_col.resize(n));
     HIP_TRY(c, d_num.resize(1));
     HIP_TRY(c, hipMemsetAsync(d_mark.p, 0, n, st));
-    HIP_TRY(c, hipEventRecord(ev0, st));
+    HIP_TRY(c, hipEventRecord(ev.a, st));
     hipLaunchKernelGGL(sites_kernel, dim3(blocks_for(n), (unsigned)((n + kSiteBand - 1) / kSiteBand)), dim3(256), 0, st,
                        (const uint8_t *)c->d_blocks_present.p, n, d_mark.p);
     HIP_TRY(c, hipGetLastError());
@@ -361,15 +318,13 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     DevBuf<char> d_temp;
     HIP_TRY(c, d_temp.resize(std::max<size_t>(temp_bytes, 1)));
     HIP_TRY(c, hipcub::DeviceSelect::Flagged(d_temp.p, temp_bytes, idx, d_mark.p, d_col.p, d_num.p, (int)n, st));
-    HIP_TRY(c, hipEventRecord(ev1, st));
+    HIP_TRY(c, hipEventRecord(ev.b, st));
     uint32_t m = 0;
     unsigned long long in_region = 0;
     HIP_TRY(c, hipMemcpyAsync(&m, d_num.p, sizeof(m), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(&in_region, d_count.p, sizeof(in_region), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
-    S.scatter_ms += ms;
+    HIP_TRY(c, ev.add_elapsed(&S.scatter_ms));
     S.pairs_in_region = in_region;
     if (m > 0) {
       std::vector<uint32_t> col(m);
@@ -401,11 +356,7 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   S.sites = c->blocks_site.size();
   S.cells_na = S.sites * S.sites - S.pairs_in_region;
   S.total_ms = ms_since(t_all);
-  if (stats != nullptr) {
-    const uint32_t want = stats->struct_size;
-    std::memcpy(stats, &S, std::min<size_t>(want, sizeof(S)));
-    stats->struct_size = want;
-  }
+  copy_stats(stats, S);
   return NGSLD_OK;
 } NGSLD_CATCH(c)
 

@@ -2,20 +2,21 @@
 // records where they are computed -- no TSV; a few hundred bin means leave the device.  DECAY.md has the rule, the deviations
 // and why the sums are exact.
 //
-//   pairs    ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into context-owned records (run_record_chunks,
-//            shared with ngsld_prune: replayed pairs carry their replayed values)
-//   bins     one wavefront per work item, one lane per candidate (ld_text.hip's mapping): the filters, dist as the TSV prints it,
-//            the right-closed bin, each chosen field as its printed value in integer micro-units (ld_prune.h).  dist rises with
-//            the candidate, so a wavefront's lanes fall in a few runs of one bin: a segmented scan merges each run and its last
-//            lane adds once, into a per-workgroup LDS histogram flushed once per workgroup (when it fits) or into global memory
-//   host     a chunk's int64 sums fold into 128-bit totals; a bin's mean is the double nearest to sum / (10^6 * rows)
+//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//            (replayed pairs carry their replayed values)
+//   bins     one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the filters,
+//            dist as the TSV prints it (dist_prefix), the right-closed bin, each chosen field as its printed value in integer
+//            micro-units (ld_prune.h).  dist rises with the candidate, so a wavefront's lanes fall in a few runs of one bin: a
+//            segmented scan merges each run and its last lane adds once, into a per-workgroup LDS histogram flushed once per
+//            workgroup (when it fits) or into global memory
+//   host     a chunk's int64 sums fold into 128-bit totals (with |q| < 2^38, a chunk of kRecordChunkPairs sums below 2^62); a
+//            bin's mean is the double nearest to sum / (10^6 * rows)
 #include "engine.h"
 #include "ld_prune.h"
+#include "ld_records.h"
 
 namespace {
 
-// records of one chunk of rows (32 B each): with |q| < 2^38, a chunk's sum stays below 2^62
-constexpr uint64_t kChunkPairs = 1ull << 24;
 // per-workgroup LDS for the histogram (configs[2]: 400 bins x (1 + 4 fields) x 8 B = 16 KB)
 constexpr uint32_t kLdsBudget = 32u << 10;
 // bins sized from the plan beyond this are refused (raise the bin size or set max_kb_dist): 2^22 bins of 250 bp span 10^9 bp
@@ -34,7 +35,7 @@ struct BinArgs {
   uint32_t n_slots;           // bins 0 .. n_slots-1
   int ns;                     // chosen fields
   int field[4];               // 0 r2_ExpG, 1 D, 2 D', 3 r2
-  int track_max;              // a chunk of more than kChunkPairs pairs: max |q| goes to meta[1]
+  int track_max;              // a chunk of more than kRecordChunkPairs pairs: max |q| goes to meta[1]
   unsigned long long *acc;    // [(1 + ns) * n_slots]: rows per bin, then the int64 sums of each field (two's complement)
   unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|, [2] a bin beyond n_slots
 };
@@ -50,10 +51,6 @@ __host__ __device__ inline long long bin_of(double d, double B) {
   while (k > 0 && !(d > (double)k * B)) --k;
   while (d > (double)(k + 1) * B) ++k;
   return k;
-}
-
-__device__ __forceinline__ double field_of(const ngsld_rec_std &r, int f) {
-  return f == 0 ? r.r2_ExpG : f == 1 ? r.D : f == 2 ? r.Dp : r.r2;
 }
 
 template <bool kLds>
@@ -80,8 +77,7 @@ __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
         const double d = printed_dist(A.cum[s2] - A.cum[s1]);
         key = bin_of(d, A.bin);
         if (((it.mask >> c) & 1ull) && key >= 0 && d < A.limit && A.maf_ok[s1] && A.maf_ok[s2]) {
-          const uint64_t k = it.first_record - A.out_base + (uint64_t)__popcll(it.mask & ((1ull << c) - 1ull));
-          const ngsld_rec_std r = A.rec[k];
+          const ngsld_rec_std r = A.rec[record_of(it, c, A.out_base)];
           take = true;
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
@@ -142,10 +138,7 @@ __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
     }
   }
   if (A.track_max) {
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long x = __shfl_xor(qmax, o);
-      qmax = x > qmax ? x : qmax;
-    }
+    qmax = wave_max(qmax);
     if (lane == 0 && qmax) atomicMax(A.meta + 1, qmax);
   }
   if (kLds) {
@@ -153,12 +146,6 @@ __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
     for (uint32_t j = threadIdx.x; j < W; j += 256)
       if (lds[j] != 0) atomicAdd(A.acc + j, lds[j]);
   }
-}
-
-inline unsigned blocks_for(uint64_t threads, unsigned per_block = 256) { return (unsigned)((threads + per_block - 1) / per_block); }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // the double nearest to a / b (round half to even) for a >= 0, 0 < b < 2^126 and a / b < 2^54 (a mean below 2^38 / 10^6):
@@ -199,9 +186,7 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   if (c == nullptr) return NGSLD_ERR_INVALID;
   const auto t_all = std::chrono::steady_clock::now();
   if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (p == nullptr || p->struct_size != sizeof(ngsld_decay_params))
-    return fail(c, NGSLD_ERR_INVALID, "ngsld_decay_params: struct_size must be sizeof(ngsld_decay_params)");
-  if (stats != nullptr && stats->struct_size < sizeof(uint32_t)) return fail(c, NGSLD_ERR_INVALID, "ngsld_decay_stats: struct_size not set");
+  if (const int rc = check_struct_sizes(c, p, "ngsld_decay_params", stats, "ngsld_decay_stats")) return rc;
   if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "decay fields must be a non-empty mask of 1, 2, 4, 8");
   if (!(p->bin_size > 1.0) || !std::isfinite(p->bin_size)) return fail(c, NGSLD_ERR_INVALID, "decay bin_size must be a finite number > 1");
   if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "decay max_kb_dist must be >= 0");
@@ -217,37 +202,22 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   std::memset(&S, 0, sizeof(S));
   S.struct_size = sizeof(S);
   hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0}, ns = 0;
-  for (int f = 0; f < 4; ++f)
-    if ((p->fields >> f) & 1u) field[ns++] = f;
+  int field[4] = {0, 0, 0, 0};
+  const int ns = field_list(p->fields, field);
   const double B = p->bin_size;
 
-  // ---- sites: dist prefix sums (ld_text.hip's), the maf filter on the printed maf ----
+  // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
   const double limit = p->max_kb_dist * 1000.0;
-  std::vector<double> cum(n);
-  std::vector<uint32_t> infc(n);
+  std::vector<double> cum;
+  std::vector<uint32_t> infc;
+  const bool exact_gaps = dist_prefix(c, cum, infc);  // integer gaps >= 0
   std::vector<uint8_t> maf_ok(n);
-  bool exact_gaps = true;  // integer gaps >= 0
-  {
-    double run = 0.0;
-    uint32_t ic = 0;
-    bool &exact = exact_gaps;
-    for (uint64_t s = 0; s < n; ++s) {
-      const double g = c->h_pos_dist.size() == n ? c->h_pos_dist[s] : std::numeric_limits<double>::infinity();
-      if (std::isinf(g) && g > 0) {
-        ++ic;
-      } else {
-        if (!(g >= 0.0) || g != std::floor(g) || run + g > 9.0e15) exact = false;
-        run += g;
-      }
-      cum[s] = run;
-      infc[s] = ic;
-      const double m = c->h_maf[s];
-      maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes, as in R)
-    }
-    if (!exact && std::isfinite(limit))
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "decay max_kb_dist needs integer position gaps");
+  for (uint64_t s = 0; s < n; ++s) {
+    const double m = c->h_maf[s];
+    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes, as in R)
   }
+  if (!exact_gaps && std::isfinite(limit))
+    return fail(c, NGSLD_ERR_UNSUPPORTED, "decay max_kb_dist needs integer position gaps");
 
   // ---- bins sized from the plan: the largest finite planned dist, capped by the limit ----
   uint64_t n_slots = 0;
@@ -282,8 +252,7 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   if (const char *e = test_knob("DECAY_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), 64u << 10);
   const bool use_lds = W > 0 && W * 8 <= lds_budget;
   S.lds = use_lds ? 1 : 0;
-  uint64_t chunk = kChunkPairs;
-  if (const char *e = test_knob("DECAY_CHUNK_PAIRS")) chunk = std::max<uint64_t>(1, std::min<uint64_t>(kChunkPairs, std::strtoull(e, nullptr, 10)));
+  const uint64_t chunk = record_chunk(test_knob("DECAY_CHUNK_PAIRS"));
 
   const uint64_t n_pairs = c->h_row_off[n];
   S.pairs = n_pairs;
@@ -303,22 +272,11 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
     HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    // records: the chunk, or the longest row when one is longer (a row is never cut)
-    uint64_t longest = 0;
-    for (uint64_t s = 0; s < n; ++s) longest = std::max<uint64_t>(longest, c->h_row_off[s + 1] - c->h_row_off[s]);
-    const uint64_t rec_cap = std::max<uint64_t>(std::min<uint64_t>(n_pairs, chunk), longest);
+    const uint64_t rec_cap = record_cap(c, chunk);
     DevBuf<ngsld_rec_std> d_rec;
     HIP_TRY(c, d_rec.resize(rec_cap));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(c, hipEventCreate(&ev0));
-    HIP_TRY(c, hipEventCreate(&ev1));
-    struct Events {
-      hipEvent_t a, b;
-      ~Events() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-      }
-    } events_{ev0, ev1};
+    EventPair ev;
+    HIP_TRY(c, ev.create());
     BinArgs A{};
     A.rec = d_rec.p;
     A.cum = d_cum.p;
@@ -335,30 +293,22 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
     const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t np) -> int {
       A.out_base = c->h_row_off[r0];
-      A.track_max = np > kChunkPairs ? 1 : 0;
-      const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
+      A.track_max = np > kRecordChunkPairs ? 1 : 0;
       HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
-      HIP_TRY(c, hipEventRecord(ev0, st));
-      const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
-      for (uint64_t off = i0; off < i1; off += max_items) {
-        A.items = c->d_items.p + off;
-        A.n_items = std::min<uint64_t>(max_items, i1 - off);
-        const unsigned blocks = std::min<unsigned>(blocks_for(A.n_items * 64), max_blocks);
+      const int rcl = launch_record_items(c, ev, r0, r1, &S.bin_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
+        A.items = items;
+        A.n_items = n_items;
+        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
         if (use_lds)
           hipLaunchKernelGGL(bin_kernel<true>, dim3(blocks), dim3(256), (size_t)W * 8, st, A);
         else
           hipLaunchKernelGGL(bin_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-        HIP_TRY(c, hipGetLastError());
-      }
-      HIP_TRY(c, hipEventRecord(ev1, st));
+      });
+      if (rcl != NGSLD_OK) return rcl;
       unsigned long long meta[3] = {0, 0, 0};
       HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      float ms = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
-      S.bin_ms += ms;
-      ++S.chunks;
       if (meta[0] != 0) {
         const unsigned long long k = meta[0] - 1;
         return fail(c, NGSLD_ERR_UNSUPPORTED, "a decay value of the pair of sites " + std::to_string(k >> 32) + " - " +
@@ -393,11 +343,7 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   c->decay_fields = p->fields;
   S.bins = c->decay_count.size();
   S.total_ms = ms_since(t_all);
-  if (stats != nullptr) {
-    const uint32_t want = stats->struct_size;
-    std::memcpy(stats, &S, std::min<size_t>(want, sizeof(S)));
-    stats->struct_size = want;
-  }
+  copy_stats(stats, S);
   return NGSLD_OK;
 } NGSLD_CATCH(c)
 

@@ -210,31 +210,41 @@ struct StoreGuard {
   }
 };
 
-// Device-side TSV: the dist column needs prefix sums of pos_dist that are EXACT (the host writer adds the gaps one by one,
-// ngsLD.cpp:241), i.e. integer gaps as read_dist produces them; otherwise (*text = false) the batches go out as records.
-static int upload_text_prefix(ngsld_ctx *c, bool *text) {
+bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc) {
   const uint64_t n = c->n_sites;
-  std::vector<double> cum(n);
-  std::vector<uint32_t> infc(n);
+  cum.resize(n);
+  infc.resize(n);
   double run = 0.0;
   uint32_t ic = 0;
-  for (uint64_t s = 0; s < n && *text; ++s) {
+  bool exact = true;
+  for (uint64_t s = 0; s < n; ++s) {
     const double g = c->h_pos_dist[s];
     if (std::isinf(g) && g > 0) {
       ++ic;
     } else {
-      if (!(g >= 0.0) || g != std::floor(g) || run + g > 9.0e15) *text = false;
+      if (!(g >= 0.0) || g != std::floor(g) || run + g > 9.0e15) exact = false;
       run += g;
     }
     cum[s] = run;
     infc[s] = ic;
   }
-  if (*text) {
-    HIP_TRY(c, c->d_cum.resize(n));
-    HIP_TRY(c, c->d_infc.resize(n));
-    HIP_TRY(c, hipMemcpy(c->d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return exact;
+}
+
+// Device-side TSV: the dist column needs the exact prefix sums of dist_prefix; without them (*text = false) the batches go out
+// as records.
+static int upload_text_prefix(ngsld_ctx *c, bool *text) {
+  std::vector<double> cum;
+  std::vector<uint32_t> infc;
+  if (!dist_prefix(c, cum, infc)) {
+    *text = false;
+    return NGSLD_OK;
   }
+  const uint64_t n = c->n_sites;
+  HIP_TRY(c, c->d_cum.resize(n));
+  HIP_TRY(c, c->d_infc.resize(n));
+  HIP_TRY(c, hipMemcpy(c->d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
   return NGSLD_OK;
 }
 
@@ -1031,9 +1041,19 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
   return check_status(c);
 }
 
+uint64_t record_cap(const ngsld_ctx *c, uint64_t chunk, const uint8_t *rows) {
+  uint64_t pairs = 0, longest = 0;
+  for (uint64_t s = 0; s < c->n_sites; ++s)
+    if (rows == nullptr || rows[s]) {
+      pairs += c->h_row_off[s + 1] - c->h_row_off[s];
+      longest = std::max<uint64_t>(longest, c->h_row_off[s + 1] - c->h_row_off[s]);
+    }
+  return std::max<uint64_t>(std::min<uint64_t>(pairs, chunk), longest);
+}
+
 int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
-                      const std::function<int(uint64_t, uint64_t, uint64_t)> &on_chunk, uint64_t row_begin, uint64_t row_end) {
-  const uint64_t n = std::min<uint64_t>(row_end, c->n_sites);
+                      const std::function<int(uint64_t, uint64_t, uint64_t)> &on_chunk, const uint8_t *rows) {
+  const uint64_t n = c->n_sites;
   // The records are read as printed (ld_prune.h): the launches flag, and the replay settles, the pairs whose sixth decimal
   // or sign rounding noise could change, as for text output -- a D one ulp off an odd / 128 tie would quantise to the other
   // neighbour than the reference's "%f"
@@ -1042,9 +1062,13 @@ int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, 
     ~FlagText() { c->dev_run_flag_text = false; }
   } flag_text{c};
   c->dev_run_flag_text = true;
-  for (uint64_t r0 = row_begin; r0 < n;) {
-    uint64_t r1 = r0 + 1;
-    while (r1 < n && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
+  for (uint64_t r0 = 0; r0 < n;) {
+    if (rows != nullptr && !rows[r0]) {
+      ++r0;
+      continue;
+    }
+    uint64_t r1 = r0 + 1;  // (a chunk ends at a row that is not run)
+    while (r1 < n && (rows == nullptr || rows[r1]) && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
     const uint64_t np = c->h_row_off[r1] - c->h_row_off[r0];
     if (np > rec_cap) return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(np) + " pairs does not fit the record buffer");
     if (np > 0) {
@@ -1052,12 +1076,28 @@ int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, 
       int rc = ngsld_run_device(c, r0, r1, d_rec, nullptr, nullptr);  // (the ctx's stream: records final, replay done)
       if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
       if (rc != NGSLD_OK) return rc;
-      if (pairs_ms) *pairs_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (pairs_ms) *pairs_ms += ms_since(t0);
       rc = on_chunk(r0, r1, np);
       if (rc != NGSLD_OK) return rc;
     }
     r0 = r1;
   }
+  return NGSLD_OK;
+}
+
+int launch_record_items(ngsld_ctx *c, EventPair &ev, uint64_t r0, uint64_t r1, double *ms, uint64_t *chunks,
+                        const std::function<void(const ngsld_item *, uint64_t)> &launch) {
+  const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
+  const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
+  HIP_TRY(c, hipEventRecord(ev.a, c->stream));
+  for (uint64_t off = i0; off < i1; off += max_items) {
+    launch(c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipEventRecord(ev.b, c->stream));
+  HIP_TRY(c, hipEventSynchronize(ev.b));
+  HIP_TRY(c, ev.add_elapsed(ms));
+  if (chunks) ++*chunks;
   return NGSLD_OK;
 }
 }  // namespace eng

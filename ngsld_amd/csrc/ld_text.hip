@@ -7,13 +7,14 @@
 // end-to-end run (9.9e7 extended rows = 15 GB): formatted here it costs a few tens of milliseconds and the host
 // only writes bytes.
 //
-// Two passes over the batch's pairs, one thread per candidate of an item: lengths, then (after an exclusive prefix
-// sum, hipCUB) the rows at their final offsets -- rows come out in (s1, s2) order, byte for byte what the host writer
-// produces.  A value outside the fast path of the formatter (>= 2^52, or a quotient beyond 63 bits: only absurd D' /
+// Two passes over the batch's pairs, one thread per candidate of an item (ld_records.h): lengths, then (after an
+// exclusive prefix sum, hipCUB) the rows at their final offsets -- rows come out in (s1, s2) order, byte for byte what the
+// host writer produces.  A value outside the fast path of the formatter (>= 2^52, or a quotient beyond 63 bits: only absurd D' /
 // chi2 of degenerate pairs get there) raises needs_host and the caller falls back to the records for that batch.
 #include <hipcub/hipcub.hpp>
 
 #include "ld_fmt.h"
+#include "ld_records.h"
 #include "ld_text.h"
 
 #ifndef NGSLD_TEXT_WORDS
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void text_kernel(TextArgs A) {
   if (i >= A.n_items) return;
   const ngsld_item it = A.items[i];
   if (c >= it.count || !((it.mask >> c) & 1ull)) return;  // ngsLD.cpp:270-282: not a computed pair
-  const uint64_t k = it.first_record - A.out_base + (uint64_t)__popcll(it.mask & ((1ull << c) - 1ull));
+  const uint64_t k = record_of(it, c, A.out_base);
   const uint32_t s1 = it.s1, s2 = it.s2_begin + c;
   if (WRITE && A.text_cap != 0 && A.offs[k] + A.lens[k] > A.text_cap) {
     *A.overflow = 1;

@@ -2,10 +2,11 @@
 // records where they are computed -- no TSV, and the graph leaves the device only as a small remainder.  PRUNE.md has the rule,
 // the deviations and why the parallel rounds end in the sequential rule's sets.
 //
-//   pairs    ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into context-owned records (replayed pairs carry
-//            their replayed values)
-//   edges    one wavefront per work item: node marks, the printed-value filter (ld_prune.h), the surviving (s1, s2, label)
-//            compacted with one ballot and one atomic per wavefront
+//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into
+//            records (replayed pairs carry their replayed values)
+//   edges    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: node
+//            marks, the printed-value filter (ld_prune.h), the surviving (s1, s2, label) compacted with one ballot and one
+//            atomic per wavefront
 //   graph    both directions of every edge radix-sorted by their first end (hipCUB): CSR offsets, neighbours, int64 weights
 //   rounds   mark (strict local maximum of (weight desc, rank asc) among the live neighbours) + remove (atomic int64 subtract
 //            on the neighbours), a wavefront per node; plain launches
@@ -15,14 +16,13 @@
 
 #include "engine.h"
 #include "ld_prune.h"
+#include "ld_records.h"
 #include "../../include/ngsld_host.h"
 
 namespace {
 
 // a round that removes fewer nodes than this hands the rest to the host
 constexpr unsigned long long kHostFinishBelow = 64;
-// records of one chunk of rows (32 B each)
-constexpr uint64_t kChunkPairs = 1ull << 24;
 
 struct EdgeArgs {
   const ngsld_item *items;
@@ -43,15 +43,6 @@ struct EdgeArgs {
   unsigned long long *meta;  // [0] edges, [1] max |label|, [2] a label < 0, [3] (s1 << 32 | s2) + 1 of a label beyond 2^62
 };
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long x = __shfl_xor(v, o);
-    v = x > v ? x : v;
-  }
-  return v;
-}
-
-// one wavefront per item, one lane per candidate (ld_text.hip's mapping)
 __global__ __launch_bounds__(256) void edge_kernel(EdgeArgs A) {
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint64_t i = t >> 6;
@@ -64,15 +55,14 @@ __global__ __launch_bounds__(256) void edge_kernel(EdgeArgs A) {
     if (c < it.count && ((it.mask >> c) & 1ull)) {
       s1 = it.s1;
       s2 = it.s2_begin + c;
-      const uint64_t k = it.first_record - A.out_base + (uint64_t)__popcll(it.mask & ((1ull << c) - 1ull));
+      const uint64_t k = record_of(it, c, A.out_base);
       const bool in1 = A.in_subset == nullptr || A.in_subset[s1], in2 = A.in_subset == nullptr || A.in_subset[s2];
       if (in1) A.node[s1] = 1;
       if (in2) A.node[s2] = 1;
       // dist as the TSV prints it (ld_text.hip format_row); not finite across a chromosome change: never an edge
       if (in1 && in2 && A.infc[s1] == A.infc[s2] && !(A.cum[s2] - A.cum[s1] > A.max_dist)) {
         const ngsld_rec_std r = A.rec[k];
-        const double x = A.field == 0 ? r.r2_ExpG : A.field == 1 ? r.D : A.field == 2 ? r.Dp : r.r2;
-        const int q = prune_label(x, A.min_weight, A.type, A.scale, &lab);
+        const int q = prune_label(field_of(r, A.field), A.min_weight, A.type, A.scale, &lab);
         if (q == kPruneEdge)
           edge = true;
         else if (q == kPruneTooLarge)
@@ -203,12 +193,6 @@ __global__ __launch_bounds__(256) void residual_kernel(const uint32_t *ea, const
   }
 }
 
-inline unsigned blocks_for(uint64_t threads, unsigned per_block = 256) { return (unsigned)((threads + per_block - 1) / per_block); }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // grow an edge list to `cap` entries, keeping the first `keep`
 template <typename T>
 hipError_t grow(DevBuf<T> &b, size_t cap, size_t keep, hipStream_t st) {
@@ -262,9 +246,7 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   if (c == nullptr) return NGSLD_ERR_INVALID;
   const auto t_all = std::chrono::steady_clock::now();
   if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (p == nullptr || p->struct_size != sizeof(ngsld_prune_params))
-    return fail(c, NGSLD_ERR_INVALID, "ngsld_prune_params: struct_size must be sizeof(ngsld_prune_params)");
-  if (stats != nullptr && stats->struct_size < sizeof(uint32_t)) return fail(c, NGSLD_ERR_INVALID, "ngsld_prune_stats: struct_size not set");
+  if (const int rc = check_struct_sizes(c, p, "ngsld_prune_params", stats, "ngsld_prune_stats")) return rc;
   if (site_state == nullptr) return fail(c, NGSLD_ERR_INVALID, "site_state is NULL");
   if (p->field < 4 || p->field > 7) return fail(c, NGSLD_ERR_INVALID, "prune field must be 4, 5, 6 or 7");
   const char type = (char)p->weight_type;
@@ -305,27 +287,10 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     for (uint64_t s = 0; s < n; ++s) in_subset[s] = want.count(lab[s]) ? 1 : 0;
   }
   const double max_dist = p->max_kb_dist * 1000.0;
-  std::vector<double> cum(n);
-  std::vector<uint32_t> infc(n);
-  {
-    double run = 0.0;
-    uint32_t ic = 0;
-    bool exact = true;
-    for (uint64_t s = 0; s < n; ++s) {
-      const double g = c->h_pos_dist.size() == n ? c->h_pos_dist[s] : std::numeric_limits<double>::infinity();
-      if (std::isinf(g) && g > 0) {
-        ++ic;
-      } else {
-        if (!(g >= 0.0) || g != std::floor(g) || run + g > 9.0e15) exact = false;
-        run += g;
-      }
-      cum[s] = run;
-      infc[s] = ic;
-    }
-    // (the TSV's dist column is the sum of the gaps one by one: exact for integer gaps, as read_dist makes them)
-    if (!exact && std::isfinite(max_dist))
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "prune max_kb_dist needs integer position gaps");
-  }
+  std::vector<double> cum;
+  std::vector<uint32_t> infc;
+  if (!dist_prefix(c, cum, infc) && std::isfinite(max_dist))
+    return fail(c, NGSLD_ERR_UNSUPPORTED, "prune max_kb_dist needs integer position gaps");
   DevBuf<double> d_cum;
   DevBuf<uint32_t> d_infc, d_rank;
   DevBuf<uint8_t> d_subset, d_node, d_mark;
@@ -353,18 +318,10 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   DevBuf<ngsld_rec_std> d_rec;
   DevBuf<uint32_t> d_ea, d_eb;
   DevBuf<int64_t> d_el;
-  const uint64_t chunk_pairs = std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, kChunkPairs));
+  const uint64_t chunk_pairs = std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, kRecordChunkPairs));  // (a longer row is refused)
   HIP_TRY(c, d_rec.resize(chunk_pairs));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(c, hipEventCreate(&ev0));
-  HIP_TRY(c, hipEventCreate(&ev1));
-  struct Events {
-    hipEvent_t a, b;
-    ~Events() {
-      (void)hipEventDestroy(a);
-      (void)hipEventDestroy(b);
-    }
-  } events_{ev0, ev1};
+  EventPair ev;
+  HIP_TRY(c, ev.create());
   EdgeArgs A{};
   A.field = p->field - 4;
   A.cum = d_cum.p;
@@ -392,21 +349,14 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     A.el = d_el.p;
     A.cap = d_el.n;
     A.out_base = c->h_row_off[r0];
-    const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-    HIP_TRY(c, hipEventRecord(ev0, st));
-    const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
-    for (uint64_t off = i0; off < i1; off += max_items) {
-      A.items = c->d_items.p + off;
-      A.n_items = std::min<uint64_t>(max_items, i1 - off);
-      hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(A.n_items * 64)), dim3(256), 0, st, A);
-      HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipEventRecord(ev1, st));
+    const int rc = launch_record_items(c, ev, r0, r1, &S.edges_ms, nullptr, [&](const ngsld_item *items, uint64_t n_items) {
+      A.items = items;
+      A.n_items = n_items;
+      hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(n_items * 64)), dim3(256), 0, st, A);
+    });
+    if (rc != NGSLD_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, ev0, ev1));
-    S.edges_ms += ms;
     if (meta[3] != 0) {
       const unsigned long long k = meta[3] - 1;
       return fail(c, NGSLD_ERR_UNSUPPORTED, "the edge label of the pair " + lab[k >> 32] + " - " + lab[k & 0xffffffffull] +
@@ -566,11 +516,7 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     S.excluded += state[s] == 2;
   }
   S.total_ms = ms_since(t_all);
-  if (stats != nullptr) {
-    const uint32_t want = stats->struct_size;
-    std::memcpy(stats, &S, std::min<size_t>(want, sizeof(S)));
-    stats->struct_size = want;
-  }
+  copy_stats(stats, S);
   return NGSLD_OK;
 } NGSLD_CATCH(c)
 
