@@ -522,6 +522,44 @@ int ngsld_blocks_matrix(ngsld_ctx *ctx, int field, double *values, uint8_t *pres
 typedef int (*ngsld_text_fn)(void *user, const char *text, uint64_t len);
 int ngsld_blocks_text(ngsld_ctx *ctx, int field, ngsld_text_fn sink, void *user, ngsld_blocks_stats *stats);
 
+/* ---- Per-site LD summaries on the device (SITES.md) -------------------------------------------------------------------------
+ * The TSV this context's plan would print, collapsed per site -- without the TSV: the pairs run again chunk by chunk into
+ * device records (every pair kernel, the exact-order replay included) and a kernel adds every counted row to BOTH of its
+ * sites.  A row counts iff dist (as printed) is finite and <= max_kb_dist * 1000, both printed maf >= min_maf, and every chosen
+ * field is finite.  Per site: the counted rows it is in, and per chosen field the sum (its LD score, the site itself not
+ * included), the maximum and the mean of the printed ("%f") values -- |value| with abs_value -- and the rows whose value is
+ * >= linked_min.  Sums and maxima are exact integers in micro-units (value * 10^6); the mean is the double nearest to the
+ * exact mean.  The rule and its deviations are in SITES.md.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_site_ld_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (default) */
+  double max_kb_dist;         /* a row needs dist <= max_kb_dist * 1000 (INFINITY: no limit, the default) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  double linked_min;          /* a row is linked in a field iff its value >= linked_min (default 0.5) */
+  int32_t abs_value;          /* != 0 (default): |value|, as pruning's weight type 'a'; 0: the signed value */
+  int32_t reserved;           /* 0 */
+} ngsld_site_ld_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_site_ld_stats) */
+  uint32_t lds;               /* 1: accumulated per tile of rows in LDS, 0: in global memory */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows that count */
+  uint64_t sites_with_pairs;  /* sites in at least one counted row */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, site_ms, total_ms;  /* pair kernels + replay, the site kernel (kernel time), the whole call */
+} ngsld_site_ld_stats;
+
+/* Summaries after ngsld_plan; the context keeps them until the next ngsld_site_ld, ngsld_plan or ngsld_set_*.  stats may be
+ * NULL.  NGSLD_ERR_UNSUPPORTED for a value of 2^38 micro-units or more (|x| >= 274877.906944, naming the pair), a site whose
+ * sum could pass 2^63 micro-units, or a finite max_kb_dist with non-integer position gaps. */
+int ngsld_site_ld(ngsld_ctx *ctx, const ngsld_site_ld_params *params, ngsld_site_ld_stats *stats);
+/* The last ngsld_site_ld's arrays of one chosen statistic (field = TSV column 4..7), n_sites entries each, any pointer may be
+ * NULL: n[] counted rows (the same for every field), sum_micro[] and max_micro[] in micro-units, linked[], mean[].  Where
+ * n[s] == 0: sum 0, linked 0, max_micro INT64_MIN, mean NaN. */
+int ngsld_site_ld_get(ngsld_ctx *ctx, int field, uint64_t *n, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked,
+                      double *mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,7 @@ SYMBOLS = [
     "ngsld_prune", "ngsld_host_prune_graph", "ngsld_host_prune_label",
     "ngsld_decay", "ngsld_decay_bins", "ngsld_host_decay_fit",
     "ngsld_blocks", "ngsld_blocks_sites", "ngsld_blocks_matrix", "ngsld_blocks_text",
+    "ngsld_site_ld", "ngsld_site_ld_get",
 ]
 
 
@@ -146,6 +147,19 @@ class BlocksStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("members", C.c_uint64), ("sites", C.c_uint64),
                 ("pairs", C.c_uint64), ("pairs_in_region", C.c_uint64), ("cells_na", C.c_uint64), ("host_rows", C.c_uint64),
                 ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("scatter_ms", C.c_double), ("format_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+class SiteLdParams(C.Structure):
+    """ngsld_site_ld_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("max_kb_dist", C.c_double), ("min_maf", C.c_double),
+                ("linked_min", C.c_double), ("abs_value", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SiteLdStats(C.Structure):
+    """ngsld_site_ld_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("sites_with_pairs", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("site_ms", C.c_double),
                 ("total_ms", C.c_double)]
 
 
@@ -283,6 +297,9 @@ def lib() -> C.CDLL:
             L.ngsld_blocks_sites.argtypes = [vp, u64, vp, C.POINTER(u64)]
             L.ngsld_blocks_matrix.argtypes = [vp, C.c_int, vp, vp]
             L.ngsld_blocks_text.argtypes = [vp, C.c_int, TEXT_FN, vp, C.POINTER(BlocksStats)]
+        if hasattr(L, "ngsld_site_ld"):
+            L.ngsld_site_ld.argtypes = [vp, C.POINTER(SiteLdParams), C.POINTER(SiteLdStats)]
+            L.ngsld_site_ld_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1026,6 +1043,33 @@ class Engine:
         for k, f in enumerate(names):
             bins[f] = mean[:nb, k].copy()
         return bins, {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}
+
+    def site_ld(self, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0, linked_min: float = 0.5,
+                abs_value: bool = True) -> tuple[dict, dict]:
+        """Per-site LD summaries of the planned pairs on the device (ngsld_site_ld, SITES.md): (sites, stats).  sites holds
+        numpy arrays of n_sites entries: "n" (counted rows) and per statistic F of ld (r2_ExpG, D, Dp, r2) "sum_F" and "max_F"
+        (int64 micro-units: value * 10^6), "linked_F" and "mean_F".  Where n is 0, max_F is the smallest int64 and mean_F NaN."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        p = SiteLdParams(C.sizeof(SiteLdParams), mask, float(max_kb_dist), float(min_maf), float(linked_min), int(bool(abs_value)), 0)
+        st = SiteLdStats()
+        st.struct_size = C.sizeof(SiteLdStats)
+        self._check(self._L.ngsld_site_ld(self._h, C.byref(p), C.byref(st)))
+        m = max(self.n_sites, 1)
+        sites = {"n": np.zeros(m, dtype=np.uint64)}
+        for k, f in enumerate(DECAY_FIELDS):
+            if not (mask >> k) & 1:
+                continue
+            sites[f"sum_{f}"], sites[f"max_{f}"] = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+            sites[f"linked_{f}"], sites[f"mean_{f}"] = np.zeros(m, dtype=np.uint64), np.zeros(m)
+            self._check(self._L.ngsld_site_ld_get(self._h, 4 + k, sites["n"].ctypes.data, sites[f"sum_{f}"].ctypes.data,
+                                                  sites[f"max_{f}"].ctypes.data, sites[f"linked_{f}"].ctypes.data,
+                                                  sites[f"mean_{f}"].ctypes.data))
+        sites = {k: v[:self.n_sites] for k, v in sites.items()}
+        return sites, {k: getattr(st, k) for k, _ in SiteLdStats._fields_ if k != "struct_size"}
 
     def blocks(self, labels: list[str], chr: str, start: int, end: int,
                ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:

@@ -16,6 +16,9 @@
 //   * --blocks_out PREFIX (new) and the other --blocks_* flags: the r2 / D' matrices of one region that scripts/LD_blocks.sh
 //     hands to LDheatmap, built on the device (ngsld_blocks, BLOCKS.md) and written as PREFIX.<stat>.tsv; taken out of argv
 //     the same way, no TSV without --out;
+//   * --site_out FILE (new) and the other --site_* flags: the pair table collapsed per site -- rows, LD score, mean, maximum
+//     and linked partners of every site -- summed on the device (ngsld_site_ld, SITES.md); taken out of argv the same way, no
+//     TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -200,6 +203,20 @@ void take_blocks_args(int *argc, char **argv, BlocksArgs *ba) {
   take_flags(argc, argv, "blocks_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &ba->given);
 }
 
+// ---- --site_* (new): per-site LD summaries on the device ----
+struct SiteArgs {
+  bool given = false;  // any --site_* flag
+  const char *out = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
+  bool is_signed = false;
+  ngsld_site_ld_params p{};
+};
+
+void take_site_args(int *argc, char **argv, SiteArgs *sa) {
+  static const char *const kValued[] = {"site_out", "site_ld", "site_max_kb_dist", "site_min_maf", "site_linked_min"};
+  const char **const dst[] = {&sa->out, &sa->ld, &sa->max_kb_dist, &sa->min_maf, &sa->linked_min};
+  take_flags(argc, argv, "site_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "site_signed", &sa->is_signed, &sa->given);
+}
+
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
   if (txt == nullptr || *txt == 0) return false;
@@ -314,7 +331,7 @@ bool parse_position(const char *txt, uint64_t *out) {
   return true;
 }
 
-// the statistics of a comma-separated list (--decay_ld, --blocks_ld) as a mask, bit k = column 4 + k; 0 when a name is unknown
+// the statistics of a comma-separated list (--decay_ld, --blocks_ld, --site_ld) as a mask, bit k = column 4 + k; 0 when a name is unknown
 uint32_t parse_ld_list(const char *txt) {
   uint32_t fields = 0;
   const std::string s = txt;
@@ -350,6 +367,27 @@ void check_blocks_args(const Params &pars, BlocksArgs *ba) {
     error(__FUNCTION__, "--blocks_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
   if (pars.in_pos == nullptr) error(__FUNCTION__, "--blocks_out needs positions: it cannot run without --pos!");
   if (pars.devices.size() > 1) error(__FUNCTION__, "--blocks_out runs on one device: it cannot be combined with --devices!");
+}
+
+void check_site_args(const Params &pars, SiteArgs *sa) {
+  if (!sa->given) return;
+  if (sa->out == nullptr) error(__FUNCTION__, "the --site_* options need --site_out FILE!");
+  if (*sa->out == 0) error(__FUNCTION__, "--site_out needs a file name!");
+  ngsld_site_ld_params &p = sa->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.linked_min = 0.5;
+  p.abs_value = sa->is_signed ? 0 : 1;
+  if (sa->ld && (p.fields = parse_ld_list(sa->ld)) == 0)
+    error(__FUNCTION__, "--site_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+  if (sa->max_kb_dist && (!parse_double(sa->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
+    error(__FUNCTION__, "--site_max_kb_dist must be a number >= 0 (or inf)!");
+  if (sa->min_maf && (!parse_double(sa->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
+    error(__FUNCTION__, "--site_min_maf must be a number >= 0!");
+  if (sa->linked_min && !parse_double(sa->linked_min, &p.linked_min)) error(__FUNCTION__, "--site_linked_min must be a number!");
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--site_out runs on one device: it cannot be combined with --devices!");
 }
 
 FILE *open_or_die(const char *path) {
@@ -409,6 +447,61 @@ void run_decay(ngsld_ctx *ctx, const Params &pars, DecayArgs &da) {
   if (pars.verbose >= 1)
     fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)st.pairs_counted,
             (unsigned long)st.pairs);
+}
+
+// a value in micro-units as exact six-decimal text
+void print_micro(FILE *f, int64_t q) {
+  const uint64_t a = q < 0 ? (uint64_t)0 - (uint64_t)q : (uint64_t)q;
+  fprintf(f, "\t%s%lu.%06lu", q < 0 ? "-" : "", (unsigned long)(a / 1000000u), (unsigned long)(a % 1000000u));
+}
+
+// one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the
+// counted rows, then sum, mean, max and linked of every chosen statistic; NA for the mean and max of a site without rows
+void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos *pos) {
+  ngsld_site_ld_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_site_ld(ctx, &sa.p, &st) != NGSLD_OK) error("ngsld_site_ld", ngsld_last_error(ctx));
+  const uint64_t n = pars.n_sites;
+  std::vector<int> fields;
+  for (int k = 0; k < 4; ++k)
+    if ((sa.p.fields >> k) & 1u) fields.push_back(k);
+  const size_t nf = fields.size();
+  std::vector<uint64_t> rows(n), linked(nf * n);
+  std::vector<int64_t> sum(nf * n), top(nf * n);
+  std::vector<double> mean(nf * n);
+  for (size_t v = 0; v < nf; ++v)
+    if (ngsld_site_ld_get(ctx, 4 + fields[v], rows.data(), sum.data() + v * n, top.data() + v * n, linked.data() + v * n,
+                          mean.data() + v * n) != NGSLD_OK)
+      error("ngsld_site_ld_get", ngsld_last_error(ctx));
+  FILE *f = fopen(sa.out, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open site LD output file!");
+  fprintf(f, "site\tn");
+  for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
+  fprintf(f, "\n");
+  for (uint64_t s = 0; s < n; ++s) {
+    if (pos) {
+      const char *lab = ngsld_host_label(pos, s);
+      fwrite(lab, 1, strcspn(lab, "\t"), f);
+    } else {
+      fprintf(f, "%lu", (unsigned long)(s + 1));
+    }
+    fprintf(f, "\t%lu", (unsigned long)rows[s]);
+    for (size_t v = 0; v < nf; ++v) {
+      print_micro(f, sum[v * n + s]);
+      if (rows[s] == 0) {
+        fprintf(f, "\tNA\tNA");
+      } else {
+        fprintf(f, "\t%.17g", mean[v * n + s]);
+        print_micro(f, top[v * n + s]);
+      }
+      fprintf(f, "\t%lu", (unsigned long)linked[v * n + s]);
+    }
+    fprintf(f, "\n");
+  }
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write site LD output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> Site LD: %lu of %lu sites in %lu of %lu pairs\n", (unsigned long)st.sites_with_pairs, (unsigned long)n,
+            (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
 }
 
 int write_blocks_text(void *user, const char *text, uint64_t len) {
@@ -899,12 +992,15 @@ int main(int argc, char **argv) {
   take_decay_args(&argc, argv, &decay);
   BlocksArgs blocks;
   take_blocks_args(&argc, argv, &blocks);
+  SiteArgs site;
+  take_site_args(&argc, argv, &site);
   parse_cmd_args(&pars, argc, argv);
   check_prune_args(pars, &prune);
   check_decay_args(pars, &decay);
   check_blocks_args(pars, &blocks);
-  // --prune_out / --decay_out / --blocks_out without --out: no TSV
-  const bool write_tsv = !(prune.given || decay.given || blocks.given) || pars.out != NULL;
+  check_site_args(pars, &site);
+  // --prune_out / --decay_out / --blocks_out / --site_out without --out: no TSV
+  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given) || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -1047,6 +1143,8 @@ int main(int argc, char **argv) {
     error(__FUNCTION__, "--decay_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0 && blocks.given)
     error(__FUNCTION__, "--blocks_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  if (slab_sites > 0 && site.given)
+    error(__FUNCTION__, "--site_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -1196,6 +1294,10 @@ int main(int argc, char **argv) {
   if (blocks.given) {  // (a pass of the pair kernels over the region's rows)
     run_blocks(ctx, pars, blocks, pos);
     timing_report.mark("LD blocks");
+  }
+  if (site.given) {  // (a pass of the pair kernels of its own)
+    run_site(ctx, pars, site, pos);
+    timing_report.mark("site LD");
   }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)

@@ -148,29 +148,6 @@ __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
   }
 }
 
-// the double nearest to a / b (round half to even) for a >= 0, 0 < b < 2^126 and a / b < 2^54 (a mean below 2^38 / 10^6):
-// long division to 55 significant bits, then the round bit and the sticky remainder
-double div_nearest(unsigned __int128 a, unsigned __int128 b) {
-  if (a == 0) return 0.0;
-  unsigned __int128 q = a / b, r = a % b;
-  int sh = 0;  // a / b = (q + r / b) * 2^-sh
-  while (q < ((unsigned __int128)1 << 54)) {
-    r <<= 1;
-    q <<= 1;
-    if (r >= b) {
-      r -= b;
-      q |= 1;
-    }
-    ++sh;
-  }
-  bool sticky = r != 0;
-  const unsigned low = (unsigned)(q & 3);
-  uint64_t m = (uint64_t)(q >> 2);
-  sticky = sticky || (low & 1);
-  if ((low & 2) && (sticky || (m & 1))) ++m;
-  return std::ldexp((double)m, 2 - sh);
-}
-
 // R's as.character of a break (15 significant digits) read back
 double break_value(uint64_t k, double B) {
   char buf[64];

@@ -33,6 +33,7 @@
 #include "../../include/ngsld.h"
 #include "ld_common.h"
 #include "ld_dispatch.h"
+#include "ld_mean.h"
 #include "ld_prep.h"
 #include "ld_replay.h"
 #include "ld_text.h"
@@ -446,6 +447,22 @@ struct ngsld_ctx {
   std::vector<double> decay_dist, decay_mean;  // decay_mean: [bin][field], fields in TSV column order
   std::vector<uint64_t> decay_count;
 
+  // the per-site summaries of the last ngsld_site_ld (site_ld.hip), until the next ngsld_site_ld, ngsld_plan or ngsld_set_*
+  // (cleared with the block matrices): rows per site, then per chosen field [rank][site] the sum and the maximum in
+  // micro-units, the linked rows and the mean
+  uint32_t site_fields = 0;
+  std::vector<uint64_t> site_n, site_linked;
+  std::vector<int64_t> site_sum, site_max;
+  std::vector<double> site_mean;
+  void clear_sites() {
+    site_fields = 0;
+    site_n.clear();
+    site_linked.clear();
+    site_sum.clear();
+    site_max.clear();
+    site_mean.clear();
+  }
+
   // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
   // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
   uint32_t blocks_fields = 0;
@@ -457,7 +474,8 @@ struct ngsld_ctx {
   std::vector<std::string> blocks_label;      // [sites] its label up to the first TAB
   DevBuf<char> d_blocks_label;                // ... back to back, for the text rows
   DevBuf<uint64_t> d_blocks_label_off;        // [sites + 1]
-  void clear_blocks() {
+  void clear_blocks() {  // (every ngsld_plan and ngsld_set_* comes through here)
+    clear_sites();
     blocks_fields = 0;
     blocks_members = 0;
     d_blocks_val.release();
@@ -542,7 +560,7 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
 // host writer adds the gaps one by one.
 bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc);
 
-// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip) and ngsld_blocks (blocks.hip) read the records of
+// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip) and ngsld_site_ld (site_ld.hip) read the records of
 // rows chunk by chunk and run a kernel of their own over each chunk's items (ld_records.h) ----
 // records of one chunk of rows (32 B each)
 constexpr uint64_t kRecordChunkPairs = 1ull << 24;

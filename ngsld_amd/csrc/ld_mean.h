@@ -1,0 +1,37 @@
+// ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
+// (site_ld.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
+// compiles it alone.
+#pragma once
+
+#include <stdint.h>
+
+#include <cmath>
+
+namespace ngsld {
+namespace eng {
+
+// the double nearest to a / b (round half to even) for a >= 0, 0 < b < 2^126 and a / b < 2^54 (a mean below 2^38 / 10^6):
+// long division to 55 significant bits, then the round bit and the sticky remainder
+inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
+  if (a == 0) return 0.0;
+  unsigned __int128 q = a / b, r = a % b;
+  int sh = 0;  // a / b = (q + r / b) * 2^-sh
+  while (q < ((unsigned __int128)1 << 54)) {
+    r <<= 1;
+    q <<= 1;
+    if (r >= b) {
+      r -= b;
+      q |= 1;
+    }
+    ++sh;
+  }
+  bool sticky = r != 0;
+  const unsigned low = (unsigned)(q & 3);
+  uint64_t m = (uint64_t)(q >> 2);
+  sticky = sticky || (low & 1);
+  if ((low & 2) && (sticky || (m & 1))) ++m;
+  return std::ldexp((double)m, 2 - sh);
+}
+
+}  // namespace eng
+}  // namespace ngsld

@@ -1,6 +1,6 @@
 // ld_records.h -- the consumer side of the pair records on the device: which record a lane of a work item reads, a TSV
-// column's field of a record, a wavefront's max.  Shared by the TSV rows (ld_text.hip) and the record passes of ngsld_prune,
-// ngsld_decay and ngsld_blocks (prune.hip, decay.hip, blocks.hip), which all map one wavefront to an item and one lane to a
+// column's field of a record, a wavefront's max and sum.  Shared by the TSV rows (ld_text.hip) and the record passes of ngsld_prune,
+// ngsld_decay, ngsld_blocks and ngsld_site_ld (prune.hip, decay.hip, blocks.hip, site_ld.hip), which all map one wavefront to an item and one lane to a
 // candidate.  Not part of the ld_device.h umbrella: the pair kernels never see it.
 #pragma once
 
@@ -28,6 +28,12 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
     const unsigned long long x = __shfl_xor(v, o);
     v = x > v ? x : v;
   }
+  return v;
+}
+
+// the sum of v over the 64 lanes, in every lane
+__device__ __forceinline__ long long wave_sum(long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
 

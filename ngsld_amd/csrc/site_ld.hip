@@ -1,0 +1,360 @@
+// site_ld.hip -- per-site LD summaries on the device (ngsld_site_ld, include/ngsld.h): the pair table collapsed per site -- rows,
+// sum (the LD score), mean, maximum and linked partners of every site -- from the pair records where they are computed; no
+// TSV, a few numbers per site leave the device.  SITES.md has the rule, the deviations and why the sums are exact.
+//
+//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//            (replayed pairs carry their replayed values)
+//   sites    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the filters,
+//            each chosen field as its printed value in integer micro-units (ld_prune.h), added to BOTH sites of the pair.
+//            The row end: the 64 lanes of an item share s1 -- rows, sums, maximum and linked rows are reduced across the
+//            wavefront and added once per item.  The column end: the lanes of an item are 64 consecutive sites, and in a
+//            windowed run the rows of a neighbourhood all hit the same few hundred columns.  A workgroup therefore takes a
+//            tile of kTileRows consecutive rows, keeps the accumulators of the sites those rows can reach -- the plan bounds
+//            the span -- in LDS and flushes the non-zero ones once, with global 64-bit atomics; where the span does not fit
+//            (all pairs, no window) every add is a global atomic.  Integer adds and maxima commute: every launch shape and
+//            order gives the same bits.
+//   host     the accumulators come back once, after the last chunk; a site's mean is the double nearest to
+//            sum / (10^6 * rows) (div_nearest, ld_mean.h)
+#include "engine.h"
+#include "ld_prune.h"
+#include "ld_records.h"
+
+namespace {
+
+// LDS of a tile's accumulators.  configs[2] (windows of ~1,000 sites), one field: (1,000 + 16) sites x 4 words x 8 B = 32 KB,
+// four workgroups (16 wavefronts) a compute unit; SITES.md has the measurements
+constexpr uint32_t kLdsBudget = 64u << 10;
+constexpr uint32_t kTileRows = 16;
+// a maximum is kept as q + kMaxBias > 0 (|q| < 2^38): 0 is "no row yet", and an unsigned max does the rest
+constexpr unsigned long long kMaxBias = 1ull << 38;
+
+struct SiteArgs {
+  const ngsld_item *items;    // the context's items, all of them
+  const uint64_t *item_off;   // ... and how many lie before each row
+  uint64_t i0, i1;            // the items of this launch
+  uint64_t r0, r1;            // the chunk's rows
+  uint64_t out_base;          // global index of the chunk's record 0
+  const ngsld_rec_std *rec;
+  const double *cum;
+  const uint32_t *infc;
+  const uint8_t *maf_ok;      // printed maf >= min_maf, per site
+  double limit;               // dist <= limit (+inf: no limit)
+  double linked_min;
+  uint32_t n_sites;
+  uint32_t cols;              // LDS path: the sites [tile's first row, + cols) have their accumulators in LDS
+  int ns;                     // chosen fields
+  int field[4];               // 0 r2_ExpG, 1 D, 2 D', 3 r2
+  int abs_value;
+  int track_max;              // a site may be in 2^25 rows or more: max |q| goes to meta[1]
+  unsigned long long *acc;    // [1 + 3 * ns][n_sites]: rows; then per field the int64 sum (two's complement), the biased maximum, the linked rows
+  unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|
+};
+
+__device__ __forceinline__ bool is_max_word(uint32_t w) { return w > 0 && (w - 1) % 3 == 1; }
+
+// word w of a site's accumulators: in the tile's LDS window where the site lies in it, else in global memory
+template <bool kLds>
+__device__ __forceinline__ void accumulate(const SiteArgs &A, unsigned long long *lds, uint32_t base, uint32_t w, uint32_t site,
+                                           unsigned long long v) {
+  unsigned long long *p = (kLds && site - base < A.cols) ? lds + (size_t)w * A.cols + (site - base) : A.acc + (size_t)w * A.n_sites + site;
+  if (is_max_word(w))
+    atomicMax(p, v);
+  else
+    atomicAdd(p, v);
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void site_kernel(SiteArgs A) {
+  extern __shared__ unsigned long long lds[];
+  const int lane = (int)__lane_id();
+  const uint32_t words = 1u + 3u * (uint32_t)A.ns;
+  uint64_t first, end, step;
+  uint32_t base = 0;
+  if (kLds) {  // a workgroup per tile of rows: its items are consecutive
+    const uint64_t ra = A.r0 + (uint64_t)blockIdx.x * kTileRows, rb = ra + kTileRows < A.r1 ? ra + kTileRows : A.r1;
+    const uint64_t ib = A.item_off[ra] > A.i0 ? A.item_off[ra] : A.i0;
+    end = A.item_off[rb] < A.i1 ? A.item_off[rb] : A.i1;
+    if (ib >= end) return;  // (the whole workgroup: nothing of this tile in this launch)
+    base = (uint32_t)ra;
+    for (uint32_t j = threadIdx.x; j < words * A.cols; j += 256) lds[j] = 0;
+    __syncthreads();
+    first = ib + (threadIdx.x >> 6);
+    step = 4;
+  } else {
+    first = A.i0 + (((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6);
+    end = A.i1;
+    step = (uint64_t)gridDim.x * 4;
+  }
+  unsigned long long qmax = 0;
+  for (uint64_t i = first; i < end; i += step) {
+    const ngsld_item it = A.items[i];
+    const uint32_t c = (uint32_t)lane;
+    const uint32_t s1 = it.s1, s2 = it.s2_begin + c;
+    bool take = false;
+    long long q[4] = {0, 0, 0, 0};
+    // (dist as the difference of the prefix sums, without decay's rounding to what "%.0f" prints: a finite limit is refused
+    // unless the gaps are integers, where the difference is the printed value, and without a limit only finiteness matters)
+    if (c < it.count && ((it.mask >> c) & 1ull) && A.infc[s1] == A.infc[s2]  // (across a chromosome dist is not finite: never counted)
+        && A.cum[s2] - A.cum[s1] <= A.limit && A.maf_ok[s1] && A.maf_ok[s2]) {
+      const ngsld_rec_std r = A.rec[record_of(it, c, A.out_base)];
+      take = true;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (v >= A.ns) break;
+        const double x = field_of(r, A.field[v]);
+        if (!(x - x == 0.0)) take = false;  // NaN or +-inf in any chosen field: the row drops out of every one
+      }
+      if (take) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          if (v >= A.ns) break;
+          int64_t m = 0;
+          if (!ngsld::printed_micro(field_of(r, A.field[v]), &m)) {
+            atomicCAS(A.meta, 0ull, (((unsigned long long)s1 << 32) | s2) + 1ull);
+            take = false;
+          }
+          q[v] = (A.abs_value && m < 0) ? -m : m;
+        }
+      }
+    }
+    const uint64_t taken = __ballot(take);
+    if (taken == 0) continue;
+    if (!take) q[0] = q[1] = q[2] = q[3] = 0;
+    // the column end: this lane's site
+    if (take) accumulate<kLds>(A, lds, base, 0, s2, 1ull);
+    const unsigned long long rows = (unsigned long long)__popcll(taken);
+    if (lane == 0) accumulate<kLds>(A, lds, base, 0, s1, rows);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      if (v >= A.ns) break;
+      const uint32_t w = 1u + 3u * (uint32_t)v;
+      const bool linked = take && (double)q[v] / 1e6 >= A.linked_min;  // the printed value read back (ld_prune.h), as doubles
+      const unsigned long long biased = take ? (unsigned long long)(q[v] + (long long)kMaxBias) : 0ull;
+      if (take) {
+        accumulate<kLds>(A, lds, base, w, s2, (unsigned long long)q[v]);
+        accumulate<kLds>(A, lds, base, w + 1, s2, biased);
+        if (linked) accumulate<kLds>(A, lds, base, w + 2, s2, 1ull);
+      }
+      // the row end: one add per item
+      const long long sum = wave_sum(q[v]);
+      const unsigned long long top = wave_max(biased);
+      const unsigned long long n_linked = (unsigned long long)__popcll(__ballot(linked));
+      if (lane == 0) {
+        accumulate<kLds>(A, lds, base, w, s1, (unsigned long long)sum);
+        accumulate<kLds>(A, lds, base, w + 1, s1, top);
+        if (n_linked) accumulate<kLds>(A, lds, base, w + 2, s1, n_linked);
+      }
+      if (A.track_max) {
+        const unsigned long long a = (unsigned long long)(q[v] < 0 ? -q[v] : q[v]);
+        qmax = a > qmax ? a : qmax;
+      }
+    }
+  }
+  if (A.track_max) {
+    qmax = wave_max(qmax);
+    if (lane == 0 && qmax) atomicMax(A.meta + 1, qmax);
+  }
+  if (kLds) {
+    __syncthreads();
+    for (uint32_t w = 0; w < words; ++w)
+      for (uint32_t col = threadIdx.x; col < A.cols; col += 256) {
+        const unsigned long long v = lds[(size_t)w * A.cols + col];
+        const uint64_t site = (uint64_t)base + col;
+        if (v == 0 || site >= A.n_sites) continue;
+        if (is_max_word(w))
+          atomicMax(A.acc + (size_t)w * A.n_sites + site, v);
+        else
+          atomicAdd(A.acc + (size_t)w * A.n_sites + site, v);
+      }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_stats *stats) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  const auto t_all = std::chrono::steady_clock::now();
+  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+  if (const int rc = check_struct_sizes(c, p, "ngsld_site_ld_params", stats, "ngsld_site_ld_stats")) return rc;
+  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "site_ld fields must be a non-empty mask of 1, 2, 4, 8");
+  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "site_ld max_kb_dist must be >= 0");
+  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "site_ld min_maf is NaN");
+  if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "site_ld linked_min is NaN");
+  const uint64_t n = c->n_sites;
+  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->clear_sites();
+  ngsld_site_ld_stats S;
+  std::memset(&S, 0, sizeof(S));
+  S.struct_size = sizeof(S);
+  hipStream_t st = c->stream;
+  int field[4] = {0, 0, 0, 0};
+  const int ns = field_list(p->fields, field);
+  const uint32_t words = 1u + 3u * (uint32_t)ns;
+
+  // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
+  const double limit = p->max_kb_dist * 1000.0;
+  std::vector<double> cum;
+  std::vector<uint32_t> infc;
+  const bool exact_gaps = dist_prefix(c, cum, infc);  // integer gaps >= 0
+  if (!exact_gaps && std::isfinite(limit))
+    return fail(c, NGSLD_ERR_UNSUPPORTED, "site_ld max_kb_dist needs integer position gaps");
+  std::vector<uint8_t> maf_ok(n);
+  for (uint64_t s = 0; s < n; ++s) {
+    const double m = c->h_maf[s];
+    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes)
+  }
+
+  // ---- from the plan: how far a row reaches (the LDS window of a tile), how many rows a site can be in (the sums' bound) ----
+  uint64_t span = 0, degree_max = 0;
+  {
+    std::vector<int64_t> cover(n + 1, 0);  // +1 where a row's candidates begin, -1 where they end
+    for (uint64_t s = 0; s < n; ++s) {
+      if (c->h_row_off[s + 1] == c->h_row_off[s] || c->h_row_end[s] <= s + 1) continue;
+      span = std::max<uint64_t>(span, c->h_row_end[s] - s - 1);
+      ++cover[s + 1];
+      --cover[c->h_row_end[s]];
+    }
+    int64_t columns = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+      columns += cover[s];
+      degree_max = std::max<uint64_t>(degree_max, (c->h_row_off[s + 1] - c->h_row_off[s]) + (uint64_t)columns);
+    }
+  }
+  const uint64_t cols = std::min<uint64_t>(span + kTileRows, n);
+  uint64_t lds_budget = kLdsBudget;
+  if (const char *e = test_knob("SITE_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), kLdsBudget);
+  const bool use_lds = span > 0 && (uint64_t)words * cols * 8 <= lds_budget;
+  S.lds = use_lds ? 1 : 0;
+  const uint64_t chunk = record_chunk(test_knob("SITE_CHUNK_PAIRS"));
+
+  const uint64_t n_pairs = c->h_row_off[n];
+  S.pairs = n_pairs;
+  const size_t W = (size_t)words * n;
+  std::vector<unsigned long long> h_acc(W, 0);
+  if (n_pairs > 0) {
+    DevBuf<double> d_cum;
+    DevBuf<uint32_t> d_infc;
+    DevBuf<uint8_t> d_maf_ok;
+    DevBuf<unsigned long long> d_acc, d_meta;
+    HIP_TRY(c, d_cum.resize(n));
+    HIP_TRY(c, d_infc.resize(n));
+    HIP_TRY(c, d_maf_ok.resize(n));
+    HIP_TRY(c, d_acc.resize(W));
+    HIP_TRY(c, d_meta.resize(2));
+    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
+    HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
+    const uint64_t rec_cap = record_cap(c, chunk);
+    DevBuf<ngsld_rec_std> d_rec;
+    HIP_TRY(c, d_rec.resize(rec_cap));
+    EventPair ev;
+    HIP_TRY(c, ev.create());
+    SiteArgs A{};
+    A.items = c->d_items.p;
+    A.item_off = c->d_item_off.p;
+    A.rec = d_rec.p;
+    A.cum = d_cum.p;
+    A.infc = d_infc.p;
+    A.maf_ok = d_maf_ok.p;
+    A.limit = limit;
+    A.linked_min = p->linked_min;
+    A.n_sites = (uint32_t)n;
+    A.cols = (uint32_t)cols;
+    A.ns = ns;
+    for (int v = 0; v < 4; ++v) A.field[v] = field[v];
+    A.abs_value = p->abs_value != 0 ? 1 : 0;
+    // every partial sum of a site is exact while max |q| * (the rows it can be in) < 2^63: certain below 2^25 rows (|q| < 2^38)
+    A.track_max = degree_max >= (1ull << 25) ? 1 : 0;
+    A.acc = d_acc.p;
+    A.meta = d_meta.p;
+    const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
+    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
+      A.out_base = c->h_row_off[r0];
+      A.r0 = r0;
+      A.r1 = r1;
+      const int rcl = launch_record_items(c, ev, r0, r1, &S.site_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
+        A.i0 = (uint64_t)(items - c->d_items.p);
+        A.i1 = A.i0 + n_items;
+        if (use_lds) {
+          const unsigned tiles = blocks_for(r1 - r0, kTileRows);
+          hipLaunchKernelGGL(site_kernel<true>, dim3(tiles), dim3(256), (size_t)words * cols * 8, st, A);
+        } else {
+          const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+          hipLaunchKernelGGL(site_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+        }
+      });
+      if (rcl != NGSLD_OK) return rcl;
+      unsigned long long bad = 0;
+      HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      if (bad != 0) {
+        const unsigned long long k = bad - 1;
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a site_ld value of the pair of sites " + std::to_string(k >> 32) + " - " +
+                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
+      }
+      return NGSLD_OK;
+    });
+    if (rc != NGSLD_OK) return rc;
+    unsigned long long meta[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (A.track_max && meta[1] > 0 && (unsigned __int128)meta[1] * degree_max >= ((unsigned __int128)1 << 63))
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "a site in up to " + std::to_string(degree_max) + " pairs with values too large to sum exactly");
+  }
+
+  // ---- the summaries: exact integer sums, one rounding for the mean ----
+  c->site_n.assign(h_acc.begin(), h_acc.begin() + n);
+  c->site_sum.resize((size_t)ns * n);
+  c->site_max.resize((size_t)ns * n);
+  c->site_linked.resize((size_t)ns * n);
+  c->site_mean.resize((size_t)ns * n);
+  uint64_t ends = 0;
+  for (uint64_t s = 0; s < n; ++s) {
+    const uint64_t rows = c->site_n[s];
+    ends += rows;
+    if (rows > 0) ++S.sites_with_pairs;
+    for (int v = 0; v < ns; ++v) {
+      const size_t w = 1 + 3 * (size_t)v, k = (size_t)v * n + s;
+      const int64_t sum = (int64_t)h_acc[w * n + s];
+      c->site_sum[k] = sum;
+      c->site_linked[k] = h_acc[(w + 2) * n + s];
+      if (rows == 0) {
+        c->site_max[k] = std::numeric_limits<int64_t>::min();
+        c->site_mean[k] = std::numeric_limits<double>::quiet_NaN();
+        continue;
+      }
+      c->site_max[k] = (int64_t)(h_acc[(w + 1) * n + s] - kMaxBias);
+      const double m = div_nearest((unsigned __int128)(sum < 0 ? -(__int128)sum : (__int128)sum), (unsigned __int128)rows * 1000000u);
+      c->site_mean[k] = sum < 0 ? -m : m;
+    }
+  }
+  S.pairs_counted = ends / 2;
+  c->site_fields = p->fields;
+  S.total_ms = ms_since(t_all);
+  copy_stats(stats, S);
+  return NGSLD_OK;
+} NGSLD_CATCH(c)
+
+int ngsld_site_ld_get(ngsld_ctx *c, int field, uint64_t *n, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean) {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  if (c->site_fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_site_ld result (it goes with the next ngsld_plan or ngsld_set_*)");
+  if (field < 4 || field > 7 || !((c->site_fields >> (field - 4)) & 1u))
+    return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_site_ld (TSV column 4..7)");
+  const size_t ns_before = (size_t)__builtin_popcount(c->site_fields & ((1u << (field - 4)) - 1u));
+  const size_t m = c->site_n.size(), k = ns_before * m;
+  if (m == 0) return NGSLD_OK;
+  if (n) std::memcpy(n, c->site_n.data(), m * sizeof(uint64_t));
+  if (sum_micro) std::memcpy(sum_micro, c->site_sum.data() + k, m * sizeof(int64_t));
+  if (max_micro) std::memcpy(max_micro, c->site_max.data() + k, m * sizeof(int64_t));
+  if (linked) std::memcpy(linked, c->site_linked.data() + k, m * sizeof(uint64_t));
+  if (mean) std::memcpy(mean, c->site_mean.data() + k, m * sizeof(double));
+  return NGSLD_OK;
+}
+
+}  // extern "C"
