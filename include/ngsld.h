@@ -560,6 +560,55 @@ int ngsld_site_ld(ngsld_ctx *ctx, const ngsld_site_ld_params *params, ngsld_site
 int ngsld_site_ld_get(ngsld_ctx *ctx, int field, uint64_t *n, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked,
                       double *mean);
 
+/* ---- LD clusters on the device (CLUSTERS.md) --------------------------------------------------------------------------------
+ * The connected components of the graph ngsld_prune prunes -- without the TSV and without an edge list: the pairs run again
+ * chunk by chunk into device records (every pair kernel, the exact-order replay included) and a kernel unites the two sites of
+ * every edge in a lock-free union-find of one word per site.  A site is a node iff it is one end of an emitted pair.  An
+ * emitted pair is an edge iff dist (as printed) is finite and <= max_kb_dist * 1000, both printed maf >= min_maf, the chosen
+ * field is finite and its printed ("%f") value -- |value| with abs_value -- is >= min_weight.  Clusters are numbered 1, 2, ...
+ * in increasing order of their smallest site, singletons included; a site that is not a node has cluster 0.  The rule and its
+ * deviations are in CLUSTERS.md.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_clusters_params) */
+  int32_t field;              /* TSV column of the edge value: 4 r2_ExpG, 5 D, 6 D', 7 r2 (default) */
+  double max_kb_dist;         /* an edge needs dist <= max_kb_dist * 1000 (INFINITY: no limit, the default) */
+  double min_maf;             /* an edge needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  double min_weight;          /* an edge needs value >= min_weight (default 0.5; a value equal to it is an edge) */
+  int32_t abs_value;          /* != 0 (default): |value|, as pruning's weight type 'a'; 0: the signed value */
+  int32_t reserved;           /* 0 */
+} ngsld_clusters_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_clusters_stats) */
+  uint32_t reserved;          /* 0 */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t nodes;             /* sites that are one end of an emitted pair */
+  uint64_t edges;             /* pairs that are edges */
+  uint64_t clusters;          /* clusters, singletons included */
+  uint64_t clusters_multi;    /* clusters of two sites or more */
+  uint64_t largest;           /* sites of the largest cluster */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  uint64_t union_launches;    /* launches of the union kernel: one per chunk (per 2^24 work items of it), whatever the diameter */
+  double pairs_ms, union_ms, finish_ms, total_ms;  /* pair kernels + replay, the union kernel (kernel time), flatten + copy
+                                                      back + the host's pass over the sites, the whole call */
+} ngsld_clusters_stats;
+
+/* Clusters after ngsld_plan; the context keeps them until the next ngsld_clusters, ngsld_plan or ngsld_set_*.  stats may be
+ * NULL.  NGSLD_ERR_UNSUPPORTED for non-integer position gaps (the limit and the spans come from the positions' prefix sums), a
+ * value of 2^38 micro-units or more (|x| >= 274877.906944, naming the pair), or a cluster whose sum could pass 2^63
+ * micro-units. */
+int ngsld_clusters(ngsld_ctx *ctx, const ngsld_clusters_params *params, ngsld_clusters_stats *stats);
+/* The last ngsld_clusters' cluster id of every site: n_sites entries, 0 for a site that is not a node. */
+int ngsld_clusters_sites(ngsld_ctx *ctx, uint32_t *cluster);
+/* The last ngsld_clusters' table: one row per cluster of at least min_size sites, in id order, up to cap rows into each array
+ * that is not NULL; *n (may be NULL) receives the number of such clusters.  first[] and last[] are the smallest and largest
+ * site index, span[] the dist the TSV would print for that pair (0 for a singleton), sum_micro[] the sum of the edges' values
+ * in micro-units (value * 10^6), mean[] the double nearest to sum / (10^6 * edges) (NaN without edges), density[] the double
+ * nearest to edges / (size * (size - 1) / 2) (NaN for a singleton). */
+int ngsld_clusters_table(ngsld_ctx *ctx, uint64_t min_size, uint64_t cap, uint32_t *id, uint32_t *size, uint32_t *first,
+                         uint32_t *last, uint64_t *span, uint64_t *edges, int64_t *sum_micro, double *mean, double *density,
+                         uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

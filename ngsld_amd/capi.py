@@ -97,6 +97,7 @@ SYMBOLS = [
     "ngsld_decay", "ngsld_decay_bins", "ngsld_host_decay_fit",
     "ngsld_blocks", "ngsld_blocks_sites", "ngsld_blocks_matrix", "ngsld_blocks_text",
     "ngsld_site_ld", "ngsld_site_ld_get",
+    "ngsld_clusters", "ngsld_clusters_sites", "ngsld_clusters_table",
 ]
 
 
@@ -161,6 +162,20 @@ class SiteLdStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
                 ("sites_with_pairs", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("site_ms", C.c_double),
                 ("total_ms", C.c_double)]
+
+
+class ClustersParams(C.Structure):
+    """ngsld_clusters_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("max_kb_dist", C.c_double), ("min_maf", C.c_double),
+                ("min_weight", C.c_double), ("abs_value", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ClustersStats(C.Structure):
+    """ngsld_clusters_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("nodes", C.c_uint64),
+                ("edges", C.c_uint64), ("clusters", C.c_uint64), ("clusters_multi", C.c_uint64), ("largest", C.c_uint64),
+                ("chunks", C.c_uint64), ("union_launches", C.c_uint64), ("pairs_ms", C.c_double), ("union_ms", C.c_double),
+                ("finish_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
@@ -300,6 +315,10 @@ def lib() -> C.CDLL:
         if hasattr(L, "ngsld_site_ld"):
             L.ngsld_site_ld.argtypes = [vp, C.POINTER(SiteLdParams), C.POINTER(SiteLdStats)]
             L.ngsld_site_ld_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        if hasattr(L, "ngsld_clusters"):
+            L.ngsld_clusters.argtypes = [vp, C.POINTER(ClustersParams), C.POINTER(ClustersStats)]
+            L.ngsld_clusters_sites.argtypes = [vp, vp]
+            L.ngsld_clusters_table.argtypes = [vp, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -1070,6 +1089,30 @@ class Engine:
                                                   sites[f"mean_{f}"].ctypes.data))
         sites = {k: v[:self.n_sites] for k, v in sites.items()}
         return sites, {k: getattr(st, k) for k, _ in SiteLdStats._fields_ if k != "struct_size"}
+
+    def clusters(self, field: int = 7, min_weight: float = 0.5, max_kb_dist: float = float("inf"), min_maf: float = 0.0,
+                 abs_value: bool = True, min_size: int = 2) -> tuple[np.ndarray, dict, dict]:
+        """LD clusters of the planned pairs on the device (ngsld_clusters, CLUSTERS.md): (cluster_ids, table, stats).
+        cluster_ids holds every site's cluster (uint32; 0: not a node; ids count singletons too).  table holds numpy arrays with
+        one entry per cluster of at least min_size sites, in id order: "id", "size", "first", "last", "span", "edges", "sum"
+        (int64 micro-units: value * 10^6), "mean" (NaN without edges) and "density" (NaN for a singleton)."""
+        p = ClustersParams(C.sizeof(ClustersParams), int(field), float(max_kb_dist), float(min_maf), float(min_weight),
+                           int(bool(abs_value)), 0)
+        st = ClustersStats()
+        st.struct_size = C.sizeof(ClustersStats)
+        self._check(self._L.ngsld_clusters(self._h, C.byref(p), C.byref(st)))
+        ids = np.zeros(max(self.n_sites, 1), dtype=np.uint32)
+        self._check(self._L.ngsld_clusters_sites(self._h, ids.ctypes.data))
+        rows = C.c_uint64(0)
+        self._check(self._L.ngsld_clusters_table(self._h, int(min_size), 0, None, None, None, None, None, None, None, None, None,
+                                                 C.byref(rows)))
+        m = max(int(rows.value), 1)
+        kinds = dict(id=np.uint32, size=np.uint32, first=np.uint32, last=np.uint32, span=np.uint64, edges=np.uint64, sum=np.int64,
+                     mean=np.float64, density=np.float64)
+        table = {k: np.zeros(m, dtype=t) for k, t in kinds.items()}
+        self._check(self._L.ngsld_clusters_table(self._h, int(min_size), m, *(table[k].ctypes.data for k in kinds), C.byref(rows)))
+        table = {k: v[:int(rows.value)] for k, v in table.items()}
+        return ids[:self.n_sites], table, {k: getattr(st, k) for k, _ in ClustersStats._fields_ if k not in ("struct_size", "reserved")}
 
     def blocks(self, labels: list[str], chr: str, start: int, end: int,
                ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:

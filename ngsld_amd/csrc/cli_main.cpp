@@ -19,6 +19,9 @@
 //   * --site_out FILE (new) and the other --site_* flags: the pair table collapsed per site -- rows, LD score, mean, maximum
 //     and linked partners of every site -- summed on the device (ngsld_site_ld, SITES.md); taken out of argv the same way, no
 //     TSV without --out;
+//   * --cluster_out FILE / --cluster_table FILE (new) and the other --cluster_* flags: the LD clusters -- the connected
+//     components of the graph --prune_out prunes -- united on the device without an edge list (ngsld_clusters, CLUSTERS.md);
+//     taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -217,6 +220,23 @@ void take_site_args(int *argc, char **argv, SiteArgs *sa) {
   take_flags(argc, argv, "site_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "site_signed", &sa->is_signed, &sa->given);
 }
 
+// ---- --cluster_* (new): LD clusters on the device ----
+struct ClusterArgs {
+  bool given = false;  // any --cluster_* flag
+  const char *out = nullptr, *table = nullptr, *field = nullptr, *min_weight = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr;
+  const char *min_size = nullptr;
+  bool is_signed = false;
+  uint64_t min_size_v = 2;
+  ngsld_clusters_params p{};
+};
+
+void take_cluster_args(int *argc, char **argv, ClusterArgs *ca) {
+  static const char *const kValued[] = {"cluster_out", "cluster_table", "cluster_field", "cluster_min_weight", "cluster_max_kb_dist",
+                                        "cluster_min_maf", "cluster_min_size"};
+  const char **const dst[] = {&ca->out, &ca->table, &ca->field, &ca->min_weight, &ca->max_kb_dist, &ca->min_maf, &ca->min_size};
+  take_flags(argc, argv, "cluster_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "cluster_signed", &ca->is_signed, &ca->given);
+}
+
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
   if (txt == nullptr || *txt == 0) return false;
@@ -390,6 +410,41 @@ void check_site_args(const Params &pars, SiteArgs *sa) {
   if (pars.devices.size() > 1) error(__FUNCTION__, "--site_out runs on one device: it cannot be combined with --devices!");
 }
 
+void check_cluster_args(const Params &pars, ClusterArgs *ca) {
+  if (!ca->given) return;
+  if (ca->out == nullptr && ca->table == nullptr)
+    error(__FUNCTION__, "the --cluster_* options need --cluster_out FILE or --cluster_table FILE!");
+  if (ca->out != nullptr && *ca->out == 0) error(__FUNCTION__, "--cluster_out needs a file name!");
+  if (ca->table != nullptr && *ca->table == 0) error(__FUNCTION__, "--cluster_table needs a file name!");
+  ngsld_clusters_params &p = ca->p;
+  p.struct_size = sizeof(p);
+  p.field = 7;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.min_weight = 0.5;
+  p.abs_value = ca->is_signed ? 0 : 1;
+  if (ca->field) {
+    char *end = nullptr;
+    const long f = strtol(ca->field, &end, 10);
+    if (*ca->field == 0 || *end != 0 || f < 4 || f > 7)
+      error(__FUNCTION__, "--cluster_field must be 4 (r2_ExpG), 5 (D), 6 (D') or 7 (r2)!");
+    p.field = (int32_t)f;
+  }
+  if (ca->min_weight && !parse_double(ca->min_weight, &p.min_weight)) error(__FUNCTION__, "--cluster_min_weight must be a number!");
+  if (ca->max_kb_dist && (!parse_double(ca->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
+    error(__FUNCTION__, "--cluster_max_kb_dist must be a number >= 0 (or inf)!");
+  if (ca->min_maf && (!parse_double(ca->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
+    error(__FUNCTION__, "--cluster_min_maf must be a number >= 0!");
+  if (ca->min_size) {
+    char *end = nullptr;
+    const bool digits = *ca->min_size >= '0' && *ca->min_size <= '9';
+    const unsigned long long v = digits ? strtoull(ca->min_size, &end, 10) : 0;
+    if (!digits || *end != 0 || v < 1 || v > 0xffffffffull) error(__FUNCTION__, "--cluster_min_size must be an integer >= 1!");
+    ca->min_size_v = v;
+  }
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--cluster_out runs on one device: it cannot be combined with --devices!");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -455,6 +510,16 @@ void print_micro(FILE *f, int64_t q) {
   fprintf(f, "\t%s%lu.%06lu", q < 0 ? "-" : "", (unsigned long)(a / 1000000u), (unsigned long)(a % 1000000u));
 }
 
+// a site as --site_out, --cluster_out and --cluster_table write it: its label up to the first TAB, without --pos its 1-based index
+void print_site(FILE *f, const ngsld_pos *pos, uint64_t s) {
+  if (pos) {
+    const char *lab = ngsld_host_label(pos, s);
+    fwrite(lab, 1, strcspn(lab, "\t"), f);
+  } else {
+    fprintf(f, "%lu", (unsigned long)(s + 1));
+  }
+}
+
 // one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the
 // counted rows, then sum, mean, max and linked of every chosen statistic; NA for the mean and max of a site without rows
 void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos *pos) {
@@ -479,12 +544,7 @@ void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos 
   for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
   fprintf(f, "\n");
   for (uint64_t s = 0; s < n; ++s) {
-    if (pos) {
-      const char *lab = ngsld_host_label(pos, s);
-      fwrite(lab, 1, strcspn(lab, "\t"), f);
-    } else {
-      fprintf(f, "%lu", (unsigned long)(s + 1));
-    }
+    print_site(f, pos, s);
     fprintf(f, "\t%lu", (unsigned long)rows[s]);
     for (size_t v = 0; v < nf; ++v) {
       print_micro(f, sum[v * n + s]);
@@ -502,6 +562,67 @@ void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos 
   if (pars.verbose >= 1)
     fprintf(stderr, "==> Site LD: %lu of %lu sites in %lu of %lu pairs\n", (unsigned long)st.sites_with_pairs, (unsigned long)n,
             (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
+}
+
+// --cluster_out: one line per site of the input, in file order, its cluster or NA; --cluster_table: one line per cluster of
+// at least --cluster_min_size sites, in id order
+void run_clusters(ngsld_ctx *ctx, const Params &pars, ClusterArgs &ca, const ngsld_pos *pos) {
+  ngsld_clusters_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_clusters(ctx, &ca.p, &st) != NGSLD_OK) error("ngsld_clusters", ngsld_last_error(ctx));
+  const uint64_t n = pars.n_sites;
+  if (ca.out) {
+    std::vector<uint32_t> id(n);
+    if (ngsld_clusters_sites(ctx, id.data()) != NGSLD_OK) error("ngsld_clusters_sites", ngsld_last_error(ctx));
+    FILE *f = fopen(ca.out, "w");
+    if (f == nullptr) error(__FUNCTION__, "cannot open LD clusters output file!");
+    fprintf(f, "site\tcluster\n");
+    for (uint64_t s = 0; s < n; ++s) {
+      print_site(f, pos, s);
+      if (id[s] == 0)
+        fprintf(f, "\tNA\n");
+      else
+        fprintf(f, "\t%u\n", id[s]);
+    }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD clusters output file!");
+  }
+  if (ca.table) {
+    uint64_t rows = 0;
+    if (ngsld_clusters_table(ctx, ca.min_size_v, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             &rows) != NGSLD_OK)
+      error("ngsld_clusters_table", ngsld_last_error(ctx));
+    std::vector<uint32_t> id(rows), size(rows), first(rows), last(rows);
+    std::vector<uint64_t> span(rows), edges(rows);
+    std::vector<int64_t> sum(rows);
+    std::vector<double> mean(rows), density(rows);
+    if (ngsld_clusters_table(ctx, ca.min_size_v, rows, id.data(), size.data(), first.data(), last.data(), span.data(), edges.data(),
+                             sum.data(), mean.data(), density.data(), nullptr) != NGSLD_OK)
+      error("ngsld_clusters_table", ngsld_last_error(ctx));
+    FILE *f = fopen(ca.table, "w");
+    if (f == nullptr) error(__FUNCTION__, "cannot open LD clusters table file!");
+    fprintf(f, "cluster\tsize\tfirst\tlast\tspan\tedges\tsum\tmean\tdensity\n");
+    for (uint64_t k = 0; k < rows; ++k) {
+      fprintf(f, "%u\t%u\t", id[k], size[k]);
+      print_site(f, pos, first[k]);
+      fprintf(f, "\t");
+      print_site(f, pos, last[k]);
+      fprintf(f, "\t%lu\t%lu", (unsigned long)span[k], (unsigned long)edges[k]);
+      print_micro(f, sum[k]);
+      if (std::isnan(mean[k]))
+        fprintf(f, "\tNA");
+      else
+        fprintf(f, "\t%.17g", mean[k]);
+      if (std::isnan(density[k]))
+        fprintf(f, "\tNA\n");
+      else
+        fprintf(f, "\t%.17g\n", density[k]);
+    }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD clusters table file!");
+  }
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD clusters: %lu of %lu sites in %lu clusters (%lu of two sites or more, the largest of %lu), %lu edges of %lu pairs\n",
+            (unsigned long)st.nodes, (unsigned long)n, (unsigned long)st.clusters, (unsigned long)st.clusters_multi,
+            (unsigned long)st.largest, (unsigned long)st.edges, (unsigned long)st.pairs);
 }
 
 int write_blocks_text(void *user, const char *text, uint64_t len) {
@@ -994,13 +1115,16 @@ int main(int argc, char **argv) {
   take_blocks_args(&argc, argv, &blocks);
   SiteArgs site;
   take_site_args(&argc, argv, &site);
+  ClusterArgs cluster;
+  take_cluster_args(&argc, argv, &cluster);
   parse_cmd_args(&pars, argc, argv);
   check_prune_args(pars, &prune);
   check_decay_args(pars, &decay);
   check_blocks_args(pars, &blocks);
   check_site_args(pars, &site);
-  // --prune_out / --decay_out / --blocks_out / --site_out without --out: no TSV
-  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given) || pars.out != NULL;
+  check_cluster_args(pars, &cluster);
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table without --out: no TSV
+  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given || cluster.given) || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -1130,7 +1254,8 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
+  } else if (!cluster.given &&  // (the clusters need the matrix resident: a job that fits is not cut only to overlap its read)
+             pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the
     // upload of one part with the pair kernels of the previous one (same output; falls back when a window is too wide).
@@ -1145,6 +1270,8 @@ int main(int argc, char **argv) {
     error(__FUNCTION__, "--blocks_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0 && site.given)
     error(__FUNCTION__, "--site_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  if (slab_sites > 0 && cluster.given)
+    error(__FUNCTION__, "--cluster_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -1298,6 +1425,10 @@ int main(int argc, char **argv) {
   if (site.given) {  // (a pass of the pair kernels of its own)
     run_site(ctx, pars, site, pos);
     timing_report.mark("site LD");
+  }
+  if (cluster.given) {  // (a pass of the pair kernels of its own)
+    run_clusters(ctx, pars, cluster, pos);
+    timing_report.mark("LD clusters");
   }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)

@@ -463,6 +463,17 @@ struct ngsld_ctx {
     site_mean.clear();
   }
 
+  // the clusters of the last ngsld_clusters (cluster.hip), until the next ngsld_clusters, ngsld_plan or ngsld_set_* (cleared
+  // with the block matrices): every site's cluster id (0: not a node), then per cluster in id order its table row
+  struct Clusters {
+    bool valid = false;
+    std::vector<uint32_t> id, size, first, last;
+    std::vector<uint64_t> span, edges;
+    std::vector<int64_t> sum;
+    std::vector<double> mean, density;
+  } clusters;
+  void clear_clusters() { clusters = Clusters(); }
+
   // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
   // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
   uint32_t blocks_fields = 0;
@@ -476,6 +487,7 @@ struct ngsld_ctx {
   DevBuf<uint64_t> d_blocks_label_off;        // [sites + 1]
   void clear_blocks() {  // (every ngsld_plan and ngsld_set_* comes through here)
     clear_sites();
+    clear_clusters();
     blocks_fields = 0;
     blocks_members = 0;
     d_blocks_val.release();
@@ -560,7 +572,7 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
 // host writer adds the gaps one by one.
 bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc);
 
-// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip) and ngsld_site_ld (site_ld.hip) read the records of
+// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip), ngsld_site_ld (site_ld.hip) and ngsld_clusters (cluster.hip) read the records of
 // rows chunk by chunk and run a kernel of their own over each chunk's items (ld_records.h) ----
 // records of one chunk of rows (32 B each)
 constexpr uint64_t kRecordChunkPairs = 1ull << 24;

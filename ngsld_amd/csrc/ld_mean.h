@@ -1,5 +1,5 @@
 // ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
-// (site_ld.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
+// (site_ld.hip) and of ngsld_clusters' clusters (cluster.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
 // compiles it alone.
 #pragma once
 
