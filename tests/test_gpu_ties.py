@@ -5,22 +5,31 @@ thousand (n_ind 8: some 1,500 of 44,850 pairs; n_ind 64: hundreds of haplotype f
 which the 1e-9 bar of the record checks lets through, turns the printed digit -- in the TSV, in LD pruning's edge labels and in
 LD decay's sums.  So on such input: (a) the records of every tie are the oracle's bits, on both kernel paths; (b) the binary's
 table is the reference program's, byte for byte; (c) LD decay's bins and (d) LD pruning's sets equal what the scripts' rules
-make of the REFERENCE program's table (not the engine's own, which a wrong device value would bend the same way).  Every case
-first asserts that it holds the ties it is about."""
+make of the REFERENCE program's table (not the engine's own, which a wrong device value would bend the same way); so do (e) the
+per-site LD summaries and (f) the LD clusters, whose sums, maxima and counts are integers of printed micro-units: with
+linked_min / min_weight on a value a tie prints (and on the value the other rounding would print), the maf filter at equality,
+on both accumulation paths, in small chunks, (g) on the generic pair kernels too, and (h) as the binary's files.  Every case
+first asserts that it holds the ties it is about, and every threshold that the reference table has rows exactly on it."""
 import ctypes as C
 import gzip
+import math
 import os
 import subprocess
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import cluster_ref
 import decay_ref
 import prune_ref
+import site_ref
 from ngsld_amd import capi, shard, synth
 from oracle import orc
-from printed_values import is_tie
+from printed_values import is_tie, micro
+from test_gpu_clusters import _same as same_clusters
 from test_gpu_decay import _same as same_bins
+from test_gpu_site_ld import _same as same_sites
 from test_gpu_vs_ref_program import same_tsv
 from util import check_records, have_ref_program, run_ref_program
 
@@ -49,6 +58,7 @@ class Case:
 
     def __init__(self, name: str, d: str):
         n_ind, kind, self.min_d, self.min_hap = CASES[name]
+        self.name = name
         self.n_ind, self.kind = n_ind, kind
         self.chrs, self.pos = synth.make_positions(N_SITES, 40 + n_ind, max_gap=300)
         self.pd = shard.pos_dist_from_positions(self.chrs, self.pos)
@@ -236,3 +246,298 @@ def test_prune_sets_of_the_reference_table(case):
         eng.close()
     print(f"prune: {checked} settings equal to the script on the reference table (min_weight {mw} a printed tie weight); "
           f"pairs with their replay {pairs_ms:.1f} ms")
+
+
+# ---- (e) - (h): per-site LD and LD clusters.  A threshold is held as q, the micro-units "%f" prints of it; the double handed to
+# the engine, the restatements and the binary is q / 10^6, what a reader makes of that text (site_ref.printed).
+ALL4 = ("r2_ExpG", "D", "Dp", "r2")
+KBS = (math.inf, 3.0, 1.0, 0.5)
+SITE_KNOBS = ("NGSLD_TEST_SITE_LDS_BYTES", "NGSLD_TEST_SITE_CHUNK_PAIRS")
+CLUSTER_KNOB = "NGSLD_TEST_CLUSTER_CHUNK_PAIRS"
+
+
+def _small(case):
+    if case.kind == "call_geno" or case.n_ind > 16:
+        pytest.skip("site LD and clusters run on the called cohorts of 8 and 16 and the text file")
+
+
+def _ties(case):
+    """The distinct tie |D| of the oracle's records, commonest first, as [(q, up)]: q the micro-units "%f" prints of it (half to
+    even), up whether that rounds the tie up -- then the raw double lies BELOW q / 10^6."""
+    vals, counts = np.unique(np.abs(case.rec["D"][case.d_ties]), return_counts=True)
+    vals = [float(vals[k]) for k in np.argsort(-counts, kind="stable")]
+    return [(micro(v), micro(v) > Fraction(v) * 10 ** 6) for v in vals]
+
+
+def _other(q, up):
+    """The tie's other neighbour: what a rounder that takes it the other way prints, on the far side of the raw double."""
+    return q - 1 if up else q + 1
+
+
+def _floors(case):
+    """The commonest tie |D|, the commonest that rounds up and the commonest that rounds down (two or three of them)."""
+    ties = _ties(case)
+    ups, downs = [t for t in ties if t[1]], [t for t in ties if not t[1]]
+    assert ups and downs, ties
+    return list(dict.fromkeys([ties[0], ups[0], downs[0]]))
+
+
+def _ref_rows(case, text):
+    """The rows of the reference program's table with a finite dist and D, as arrays (site1, site2, |D| in micro-units, dist):
+    what the thresholds are counted on, and what the search of _structured runs over."""
+    if not hasattr(case, "rows"):
+        index = {lab: k for k, lab in enumerate(case.labels)}
+        out = []
+        for ln in text.splitlines():
+            f = ln.split("\t")
+            if not ln or f[0] == "site1" or f[2].strip().lstrip("+-").lower() in ("inf", "nan"):
+                continue
+            q = site_ref.micro(f[4])
+            if q is not None:
+                out.append((index[f[0]], index[f[1]], abs(q), int(f[2])))
+        case.rows = tuple(np.array(out, dtype=np.int64).T)
+    return case.rows
+
+
+def _on(rows, q, kb=math.inf):
+    """Rows within kb whose |D| prints exactly q: the boundary rows of a floor q / 10^6."""
+    return int(np.count_nonzero((rows[2] == q) & (rows[3] <= kb * 1000)))
+
+
+def _from(rows, q, kb=math.inf):
+    return int(np.count_nonzero((rows[2] >= q) & (rows[3] <= kb * 1000)))
+
+
+def _components(n, a, b):
+    """Every site's smallest connected site over the edges (a[k], b[k]) (numpy: only the search below uses it)."""
+    lab = np.arange(n)
+    while True:
+        new = lab.copy()
+        low = np.minimum(lab[a], lab[b])
+        np.minimum.at(new, a, low)
+        np.minimum.at(new, b, low)
+        new = new[new]
+        if np.array_equal(new, lab):
+            return lab
+        lab = new
+
+
+def _structured(case, text):
+    """(q, up, kb): a tie floor x max_kb_dist of KBS, ties commonest first, with an edge exactly on the floor that leaves at least
+    three clusters of three sites and a singleton -- the first at which the components change when the floor moves one
+    micro-unit up if there is one, else the first of all.  Where no setting has that shape (text_n8_missing: near pairs are in
+    strong LD there, and within 3 kb only the two highest tie floors, with one and five edges on them, leave more than one
+    cluster of three sites) the one with an edge on the floor and the most clusters of three sites, then the most edges on it.
+    None without any.  A search: the test then asserts what it found with the restatement."""
+    if not hasattr(case, "structured"):
+        s1, s2, qd, dist = _ref_rows(case, text)
+        first, best = None, None
+        for q, up in _ties(case):
+            for kb in KBS:
+                near = dist <= kb * 1000
+                on = int(np.count_nonzero(near & (qd == q)))
+                if not on:
+                    continue
+                lab = _components(N_SITES, s1[near & (qd >= q)], s2[near & (qd >= q)])
+                size = np.bincount(lab, minlength=N_SITES)
+                big, single = int(np.count_nonzero(size >= 3)), int(np.count_nonzero(size == 1))
+                if single >= 1 and (best is None or (big, on) > best[0]):
+                    best = ((big, on), (q, up, kb))
+                if big < 3 or single < 1:
+                    continue
+                first = first or (q, up, kb)
+                if not np.array_equal(lab, _components(N_SITES, s1[near & (qd > q)], s2[near & (qd > q)])):
+                    case.structured = (q, up, kb)
+                    return case.structured
+        case.structured = first or (best and best[1])
+    return case.structured
+
+
+def _cached(fn, text, labels, **fixed):
+    """fn(text, labels, **fixed, **kw), computed once per kw: the restatements take a moment over 44,850 rows."""
+    seen = {}
+
+    def want(**kw):
+        key = tuple(sorted(kw.items()))
+        if key not in seen:
+            seen[key] = fn(text, labels, **fixed, **kw)
+        return seen[key]
+    return want
+
+
+@needs_ref
+def test_site_ld_of_the_reference_table(case, monkeypatch):
+    """(e) per-site LD on the device against the rule of SITES.md on the reference program's table, integers equal and means
+    bit for bit: all four statistics signed and absolute, with the LDS and the global accumulators and in chunks of 3,000
+    pairs; linked_min on the value a tie prints and on the one the other rounding would print; min_maf a printed frequency;
+    a distance limit inside the data.  (g) called_n8 once more on the generic pair kernels."""
+    _small(case)
+    text = _ref_table(case, True, os.path.dirname(case.ppath))
+    rows = _ref_rows(case, text)
+    floors = _floors(case)
+    top = floors[0][0] / 10 ** 6
+    min_maf = 1.0 / case.n_ind
+    assert f"\t{min_maf:f}\t" in text
+    want = _cached(site_ref.site_ld, text, case.labels)
+    for k in SITE_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("NGSLD_TEST_HARD_KERNEL", raising=False)
+
+    def check(eng, **kw):
+        sites, stats = eng.site_ld(**kw)
+        w = want(**kw)
+        same_sites(sites, w, kw["ld"])
+        assert stats["pairs"] == len(case.rec) and stats["pairs_counted"] * 2 == sum(w["n"]) > 0
+        return stats, w
+
+    all4 = dict(ld=ALL4, linked_min=top, abs_value=False)
+    eng = case.engine()
+    try:
+        eng.plan(extend_out=True)
+        st, signed = check(eng, **all4)
+        assert st["lds"] == 1
+        monkeypatch.setenv(SITE_KNOBS[0], "0")
+        assert check(eng, **all4)[0]["lds"] == 0
+        monkeypatch.delenv(SITE_KNOBS[0])
+        monkeypatch.setenv(SITE_KNOBS[1], "3000")
+        st, _ = check(eng, **all4)
+        assert st["lds"] == 1 and st["chunks"] > 5
+        monkeypatch.delenv(SITE_KNOBS[1])
+        _, absolute = check(eng, ld=ALL4, linked_min=top, abs_value=True)
+        assert signed["sum_D"] != absolute["sum_D"] and signed["linked_D"] != absolute["linked_D"]  # (negative D, some beyond -top)
+        notes = []
+        for q, up in floors:
+            _, w = check(eng, ld=("D",), linked_min=q / 10 ** 6)
+            _, o = check(eng, ld=("D",), linked_min=_other(q, up) / 10 ** 6)
+            on, linked, other = _on(rows, q), sum(w["linked_D"]), sum(o["linked_D"])
+            assert on > 0 and linked == 2 * _from(rows, q)
+            # rounded down: the other neighbour lies above, the boundary rows are linked at q and not at q + 1; rounded up: it
+            # lies below, and they are linked at both
+            assert (other - linked == 2 * _on(rows, q - 1)) if up else (linked - other == 2 * on)
+            notes.append(f"{q / 10 ** 6:f} ({'up' if up else 'down'}, {on} rows on it, linked ends {linked} / {other} at its other neighbour)")
+        check(eng, ld=("D",), linked_min=top, min_maf=min_maf)
+        _, w = check(eng, ld=("D", "r2"), linked_min=top, max_kb_dist=1.0)
+        assert 0 < sum(w["n"]) < sum(absolute["n"])
+    finally:
+        eng.close()
+    print(f"site LD: linked_min on the printed ties {'; '.join(notes)}; min_maf {min_maf:f}; equal to the rule on the reference table")
+    if case.name == "called_n8":
+        monkeypatch.setenv("NGSLD_TEST_HARD_KERNEL", "0")
+        eng = case.engine()
+        try:
+            assert eng.pair_kernel() != "hard"
+            eng.plan(extend_out=True)
+            check(eng, **all4)
+        finally:
+            eng.close()
+        print("site LD: the same on the generic pair kernels")
+
+
+def _edges(table):
+    return sum(r["edges"] for r in table)
+
+
+def _shape(table):
+    return sum(1 for r in table if r["size"] >= 3), sum(1 for r in table if r["size"] == 1)
+
+
+@needs_ref
+def test_clusters_of_the_reference_table(case, monkeypatch):
+    """(f) LD clusters on D (field 5) on the device against the rule of CLUSTERS.md on the reference program's table, ids and
+    integers equal, means and densities bit for bit: the floor on the commonest printed tie |D|; a structured setting (a tie floor
+    and a distance limit that leave three clusters of three sites, a singleton and edges exactly on the floor -- for called_n8 one
+    whose ids change without those edges); the floors the other rounding would print; signed D; min_maf a printed frequency;
+    chunks of 3,000 pairs; LD pruning's graph of the same setting.  (g) called_n8 once more on the generic pair kernels."""
+    _small(case)
+    text = _ref_table(case, True, os.path.dirname(case.ppath))
+    rows = _ref_rows(case, text)
+    min_maf = 1.0 / case.n_ind
+    assert f"\t{min_maf:f}\t" in text
+    want = _cached(cluster_ref.clusters, text, case.labels, min_size=1, field=5)
+    monkeypatch.delenv(CLUSTER_KNOB, raising=False)
+    monkeypatch.delenv("NGSLD_TEST_HARD_KERNEL", raising=False)
+
+    def check(eng, **kw):
+        ids, table, stats = eng.clusters(field=5, min_size=1, **kw)
+        w_ids, w_table = want(**kw)
+        same_clusters(ids, table, w_ids, w_table)
+        assert stats["pairs"] == len(case.rec) and stats["edges"] == _edges(w_table) > 0
+        assert stats["nodes"] == sum(1 for k in w_ids if k) and stats["clusters"] == len(w_table)
+        return ids, stats
+
+    # the settings and what the reference table holds at them, before the device is asked
+    top = _floors(case)[0][0]
+    assert _on(rows, top) > 0 and _edges(want(min_weight=top / 10 ** 6)[1]) == _from(rows, top)
+    found = _structured(case, text)
+    assert found is not None, "no tie floor leaves a singleton and has an edge on it"
+    q, up, kb = found
+    floor = q / 10 ** 6
+    here = dict(min_weight=floor, max_kb_dist=kb)
+    w_ids, w_table = want(**here)
+    above_ids, above_table = want(min_weight=(q + 1) / 10 ** 6, max_kb_dist=kb)
+    on, (big, single) = _on(rows, q, kb), _shape(w_table)
+    assert on > 0 and _edges(w_table) == _from(rows, q, kb) == _edges(above_table) + on
+    # (the text file has no tie floor of that shape -- _structured -- and is held to more than one cluster of three sites)
+    assert big >= (3 if case.kind == "bin" else 2) and single >= 1, (big, single)
+    ids_change = w_ids != above_ids
+    assert ids_change or case.name != "called_n8"
+    q2, up2 = next(t for t in _ties(case) if t[1] != up and _on(rows, t[0], kb) > 0)   # (a tie that rounds the other way)
+    print(f"clusters: floor {top / 10 ** 6:f} with {_on(rows, top)} of {_from(rows, top)} edges on it; structured setting "
+          f"{floor:f} ({'up' if up else 'down'}) at {kb} kb: {len(w_table)} clusters ({big} of three sites, {single} singletons), "
+          f"{on} of {_edges(w_table)} edges on the floor, ids {'change' if ids_change else 'stay'} without them; other neighbours "
+          f"{_other(q, up) / 10 ** 6:f} and {_other(q2, up2) / 10 ** 6:f} ({_on(rows, q2, kb)} edges on {q2 / 10 ** 6:f})")
+
+    eng = case.engine()
+    try:
+        eng.plan(extend_out=True)
+        check(eng, min_weight=top / 10 ** 6)
+        ids, st = check(eng, **here)
+        check(eng, min_weight=_other(q, up) / 10 ** 6, max_kb_dist=kb)
+        check(eng, min_weight=_other(q2, up2) / 10 ** 6, max_kb_dist=kb)
+        check(eng, abs_value=False, **here)
+        assert 0 < _edges(want(abs_value=False, **here)[1]) < _edges(w_table)   # (negative D beyond -floor)
+        check(eng, min_maf=min_maf, **here)
+        monkeypatch.setenv(CLUSTER_KNOB, "3000")
+        assert check(eng, **here)[1]["chunks"] > 5
+        monkeypatch.delenv(CLUSTER_KNOB)
+        state, pst = eng.prune(case.labels, field=5, weight_type="a", min_weight=floor, max_kb_dist=kb)
+        assert pst["edges"] == st["edges"] == _edges(w_table) and np.array_equal(state != 0, ids != 0)
+        assert pst["nodes"] == st["nodes"] == sum(1 for k in w_ids if k)
+    finally:
+        eng.close()
+    if case.name == "called_n8":
+        monkeypatch.setenv("NGSLD_TEST_HARD_KERNEL", "0")
+        eng = case.engine()
+        try:
+            assert eng.pair_kernel() != "hard"
+            eng.plan(extend_out=True)
+            check(eng, **here)
+        finally:
+            eng.close()
+        print("clusters: the same on the generic pair kernels")
+
+
+@needs_ref
+def test_site_and_cluster_files_of_the_reference_table(case, tmp_path):
+    """(h) one run of the binary: --site_out, --cluster_out and --cluster_table, linked_min and the floor on printed ties, are
+    the files the restatements write from the reference program's table, byte for byte."""
+    if case.name not in ("called_n8", "text_n8_missing"):
+        pytest.skip("the binary's files are checked on the called cohort of 8 and the text file")
+    text = _ref_table(case, True, os.path.dirname(case.ppath))
+    rows = _ref_rows(case, text)
+    top = _floors(case)[0][0]
+    q, _, kb = _structured(case, text)
+    assert _on(rows, top) > 0 and _on(rows, q, kb) > 0
+    env = {k: v for k, v in os.environ.items() if not k.startswith("NGSLD_")}
+    s, c, k = (str(tmp_path / f) for f in ("s.tsv", "c.tsv", "k.tsv"))
+    h = subprocess.run([capi.CLI_PATH, *case.flags, "--extend_out", "--n_threads", "2",
+                        "--site_out", s, "--site_ld", "D,r2", "--site_linked_min", repr(top / 10 ** 6),
+                        "--cluster_out", c, "--cluster_table", k, "--cluster_field", "5", "--cluster_min_weight", repr(q / 10 ** 6),
+                        "--cluster_max_kb_dist", repr(kb), "--cluster_min_size", "1"], capture_output=True, text=True, timeout=300, env=env)
+    assert h.returncode == 0, h.stderr[-2000:]
+    assert open(s).read() == site_ref.site_file(text, case.labels, ld=("D", "r2"), linked_min=top / 10 ** 6)
+    ids, table = cluster_ref.clusters(text, case.labels, min_size=1, field=5, min_weight=q / 10 ** 6, max_kb_dist=kb)
+    assert open(c).read() == cluster_ref.cluster_file(ids, case.labels)
+    assert open(k).read() == cluster_ref.table_file(table, case.labels)
+    print(f"files: linked_min {top / 10 ** 6:f} ({_on(rows, top)} rows on it), floor {q / 10 ** 6:f} at {kb} kb ({_on(rows, q, kb)} edges "
+          f"on it): {N_SITES} sites and {len(table)} clusters identical")
