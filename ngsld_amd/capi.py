@@ -944,6 +944,22 @@ class Engine:
         return (cat(s1s, np.uint64), cat(s2s, np.uint64), cat(stds, REC_STD),
                 cat(exts, REC_EXT) if self.extend_out else None)
 
+    def items(self, s1_begin: int = 0, s1_end: int | None = None) -> np.ndarray:
+        """The work items (dtype ITEM) of rows [s1_begin, s1_end), as a record run's batches hand them to the sink; leaves
+        device-side text output off."""
+        s1_end = self.n_sites if s1_end is None else s1_end
+        got = []
+
+        def sink(_user, bp):
+            b = bp.contents
+            if b.n_items:
+                got.append(np.frombuffer(C.string_at(b.items, b.n_items * ITEM.itemsize), dtype=ITEM).copy())
+            return 0
+
+        self.set_text_output(None, False)
+        self._check(self._L.ngsld_run(self._h, s1_begin, s1_end, SINK_FN(sink), None))
+        return np.concatenate(got) if got else np.zeros(0, dtype=ITEM)
+
     def run_to_fd(self, s1_begin: int, s1_end: int, fd: int, pos_handle, pos_dist: np.ndarray | None, maf: np.ndarray,
                   n_threads: int) -> int:
         """Rows [s1_begin, s1_end) -> TSV rows on file descriptor fd: text batches (after set_text_output) are written
