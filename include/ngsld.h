@@ -609,6 +609,59 @@ int ngsld_clusters_table(ngsld_ctx *ctx, uint64_t min_size, uint64_t cap, uint32
                          uint32_t *last, uint64_t *span, uint64_t *edges, int64_t *sum_micro, double *mean, double *density,
                          uint64_t *n);
 
+/* ---- LD grid on the device (GRID.md) ----------------------------------------------------------------------------------------
+ * The TSV this context's plan would print, binned into a heat map along each chromosome -- without the TSV: the pairs run again
+ * chunk by chunk into device records (every pair kernel, the exact-order replay included) and a kernel adds every counted row to
+ * ONE cell.  A site's position p and chromosome come from its label (up to the first TAB: CHR ":" p); its bin is p / bin_size in
+ * integer division; a counted row (s1, s2) belongs to the cell (chromosome, bin(s1), bin(s2)).  A row counts iff dist (as
+ * printed) is finite and <= max_kb_dist * 1000, both printed maf >= min_maf, and every chosen field is finite.  Per cell: the
+ * counted rows, and per chosen field the sum, the maximum and the mean of the printed ("%f") values -- |value| with abs_value --
+ * and the rows whose value is >= linked_min.  Sums and maxima are exact integers in micro-units (value * 10^6); the mean is the
+ * double nearest to the exact mean.  The rule and its refusals are in GRID.md.  Both structs start with struct_size, as the
+ * pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_grid_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (default) */
+  uint64_t bin_size;          /* B: the window in bp, 1 <= B < 2^31 */
+  double max_kb_dist;         /* a row needs dist <= max_kb_dist * 1000 (INFINITY: no limit, the default) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  double linked_min;          /* a row is linked in a field iff its value >= linked_min (default 0.5) */
+  int32_t abs_value;          /* != 0 (default): |value|, as pruning's weight type 'a'; 0: the signed value */
+  int32_t reserved;           /* 0 */
+} ngsld_grid_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_grid_stats) */
+  uint32_t lds;               /* 1: accumulated per tile of rows in LDS, 0: in global memory */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows that count: the sum of n over the cells */
+  uint64_t cells;             /* cells with rows (what ngsld_grid_cells returns) */
+  uint64_t bins;              /* bins between the first and the last site of every chromosome */
+  uint64_t band;              /* K: the bins a row's candidates reach, from the plan; the accumulators hold bins x K cells */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, grid_ms, total_ms;  /* pair kernels + replay, the grid kernel (kernel time), the whole call */
+} ngsld_grid_stats;
+
+/* The grid after ngsld_plan; the context keeps it until the next ngsld_grid, ngsld_plan or ngsld_set_*.  labels = n_sites C
+ * strings, the TSV's first two columns (NULL or "(null)" labels: NGSLD_ERR_INVALID, the grid needs positions).  stats may be
+ * NULL.  NGSLD_ERR_UNSUPPORTED, naming the site, for a position that is not plain decimal digits, positions that decrease
+ * inside a chromosome, a chromosome name that begins two runs of sites, or label chromosomes that disagree with pos_dist (a
+ * chromosome changes exactly where the gap is +inf); also for a value of 2^38 micro-units or more (|x| >= 274877.906944, naming
+ * the pair), a cell whose sum could pass 2^63 micro-units, a finite max_kb_dist with non-integer position gaps, or accumulators
+ * of more than 2 GiB ((1 + 3 x fields) x bins x band x 8 B: a larger bin_size is needed). */
+int ngsld_grid(ngsld_ctx *ctx, const ngsld_grid_params *params, const char *const *labels, ngsld_grid_stats *stats);
+/* The last ngsld_grid's cells with rows, ordered by chromosome (file order), bin1, bin2: up to cap of them into chr[] (index
+ * into ngsld_grid_chromosomes' names), bin1[] and bin2[] (the bins b = p / bin_size of the pair's first and second site; the
+ * window is [b * bin_size, (b + 1) * bin_size)) and n[] (rows).  Any pointer may be NULL; *n_cells (may be NULL) receives the
+ * number of cells. */
+int ngsld_grid_cells(ngsld_ctx *ctx, uint64_t cap, uint32_t *chr, uint64_t *bin1, uint64_t *bin2, uint64_t *n, uint64_t *n_cells);
+/* The chromosomes of the last ngsld_grid in file order: up to cap names into name[] (the context's strings: valid while the
+ * result is); *n_chr (may be NULL) receives their number. */
+int ngsld_grid_chromosomes(ngsld_ctx *ctx, uint64_t cap, const char **name, uint64_t *n_chr);
+/* The last ngsld_grid's arrays of one chosen statistic (field = TSV column 4..7), in the order of ngsld_grid_cells, up to cap
+ * entries each, any pointer may be NULL: sum_micro[] and max_micro[] in micro-units, linked[], mean[]. */
+int ngsld_grid_get(ngsld_ctx *ctx, int field, uint64_t cap, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,7 @@ SYMBOLS = [
     "ngsld_blocks", "ngsld_blocks_sites", "ngsld_blocks_matrix", "ngsld_blocks_text",
     "ngsld_site_ld", "ngsld_site_ld_get",
     "ngsld_clusters", "ngsld_clusters_sites", "ngsld_clusters_table",
+    "ngsld_grid", "ngsld_grid_cells", "ngsld_grid_chromosomes", "ngsld_grid_get",
 ]
 
 
@@ -176,6 +177,19 @@ class ClustersStats(C.Structure):
                 ("edges", C.c_uint64), ("clusters", C.c_uint64), ("clusters_multi", C.c_uint64), ("largest", C.c_uint64),
                 ("chunks", C.c_uint64), ("union_launches", C.c_uint64), ("pairs_ms", C.c_double), ("union_ms", C.c_double),
                 ("finish_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class GridParams(C.Structure):
+    """ngsld_grid_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("bin_size", C.c_uint64), ("max_kb_dist", C.c_double),
+                ("min_maf", C.c_double), ("linked_min", C.c_double), ("abs_value", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GridStats(C.Structure):
+    """ngsld_grid_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("cells", C.c_uint64), ("bins", C.c_uint64), ("band", C.c_uint64), ("chunks", C.c_uint64),
+                ("pairs_ms", C.c_double), ("grid_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
@@ -319,6 +333,11 @@ def lib() -> C.CDLL:
             L.ngsld_clusters.argtypes = [vp, C.POINTER(ClustersParams), C.POINTER(ClustersStats)]
             L.ngsld_clusters_sites.argtypes = [vp, vp]
             L.ngsld_clusters_table.argtypes = [vp, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
+        if hasattr(L, "ngsld_grid"):
+            L.ngsld_grid.argtypes = [vp, C.POINTER(GridParams), C.POINTER(C.c_char_p), C.POINTER(GridStats)]
+            L.ngsld_grid_cells.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
+            L.ngsld_grid_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
+            L.ngsld_grid_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1129,6 +1148,48 @@ class Engine:
         self._check(self._L.ngsld_clusters_table(self._h, int(min_size), m, *(table[k].ctypes.data for k in kinds), C.byref(rows)))
         table = {k: v[:int(rows.value)] for k, v in table.items()}
         return ids[:self.n_sites], table, {k: getattr(st, k) for k, _ in ClustersStats._fields_ if k not in ("struct_size", "reserved")}
+
+    def grid(self, labels: list[str] | None, bin_size: int, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0,
+             linked_min: float = 0.5, abs_value: bool = True) -> tuple[dict, dict]:
+        """The LD grid of the planned pairs on the device (ngsld_grid, GRID.md): (cells, stats).  cells holds numpy arrays with
+        one entry per cell with rows, ordered by chromosome (file order), bin1, bin2: "chr" (the chromosome's name), "bin1" and
+        "bin2" (the lower breaks b * bin_size of the windows of the pair's first and second site, as --grid_out writes them), "n"
+        (counted rows) and per statistic F of ld (r2_ExpG, D, Dp, r2) "sum_F" and "max_F" (int64 micro-units: value * 10^6),
+        "linked_F" and "mean_F"."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        arr = None if labels is None else (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels])
+        p = GridParams(C.sizeof(GridParams), mask, int(bin_size), float(max_kb_dist), float(min_maf), float(linked_min),
+                       int(bool(abs_value)), 0)
+        st = GridStats()
+        st.struct_size = C.sizeof(GridStats)
+        self._check(self._L.ngsld_grid(self._h, C.byref(p), arr, C.byref(st)))
+        nc = int(st.cells)
+        m = max(nc, 1)
+        n_chr = C.c_uint64(0)
+        self._check(self._L.ngsld_grid_chromosomes(self._h, 0, None, C.byref(n_chr)))
+        names = (C.c_char_p * max(int(n_chr.value), 1))()
+        self._check(self._L.ngsld_grid_chromosomes(self._h, int(n_chr.value), names, None))
+        names = np.array([names[k].decode() for k in range(int(n_chr.value))] or [""])
+        idx, b1, b2 = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+        cells = {"n": np.zeros(m, dtype=np.uint64)}
+        got = C.c_uint64(0)
+        self._check(self._L.ngsld_grid_cells(self._h, m, idx.ctypes.data, b1.ctypes.data, b2.ctypes.data, cells["n"].ctypes.data,
+                                             C.byref(got)))
+        assert got.value == nc
+        cells = {"chr": names[idx], "bin1": b1 * np.uint64(int(bin_size)), "bin2": b2 * np.uint64(int(bin_size)), **cells}
+        for k, f in enumerate(DECAY_FIELDS):
+            if not (mask >> k) & 1:
+                continue
+            cells[f"sum_{f}"], cells[f"max_{f}"] = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+            cells[f"linked_{f}"], cells[f"mean_{f}"] = np.zeros(m, dtype=np.uint64), np.zeros(m)
+            self._check(self._L.ngsld_grid_get(self._h, 4 + k, m, cells[f"sum_{f}"].ctypes.data, cells[f"max_{f}"].ctypes.data,
+                                               cells[f"linked_{f}"].ctypes.data, cells[f"mean_{f}"].ctypes.data))
+        cells = {k: v[:nc] for k, v in cells.items()}
+        return cells, {k: getattr(st, k) for k, _ in GridStats._fields_ if k != "struct_size"}
 
     def blocks(self, labels: list[str], chr: str, start: int, end: int,
                ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:

@@ -22,6 +22,9 @@
 //   * --cluster_out FILE / --cluster_table FILE (new) and the other --cluster_* flags: the LD clusters -- the connected
 //     components of the graph --prune_out prunes -- united on the device without an edge list (ngsld_clusters, CLUSTERS.md);
 //     taken out of argv the same way, no TSV without --out;
+//   * --grid_out FILE --grid_bin_size B (new) and the other --grid_* flags: the LD heat map along each chromosome -- rows, sum,
+//     mean, maximum and linked rows of the site pairs between every two windows of B bp -- binned on the device (ngsld_grid,
+//     GRID.md); taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -237,6 +240,20 @@ void take_cluster_args(int *argc, char **argv, ClusterArgs *ca) {
   take_flags(argc, argv, "cluster_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "cluster_signed", &ca->is_signed, &ca->given);
 }
 
+// ---- --grid_* (new): the LD grid on the device ----
+struct GridArgs {
+  bool given = false;  // any --grid_* flag
+  const char *out = nullptr, *bin_size = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
+  bool is_signed = false;
+  ngsld_grid_params p{};
+};
+
+void take_grid_args(int *argc, char **argv, GridArgs *ga) {
+  static const char *const kValued[] = {"grid_out", "grid_bin_size", "grid_ld", "grid_max_kb_dist", "grid_min_maf", "grid_linked_min"};
+  const char **const dst[] = {&ga->out, &ga->bin_size, &ga->ld, &ga->max_kb_dist, &ga->min_maf, &ga->linked_min};
+  take_flags(argc, argv, "grid_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "grid_signed", &ga->is_signed, &ga->given);
+}
+
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
   if (txt == nullptr || *txt == 0) return false;
@@ -445,6 +462,31 @@ void check_cluster_args(const Params &pars, ClusterArgs *ca) {
   if (pars.devices.size() > 1) error(__FUNCTION__, "--cluster_out runs on one device: it cannot be combined with --devices!");
 }
 
+void check_grid_args(const Params &pars, GridArgs *ga) {
+  if (!ga->given) return;
+  if (ga->out == nullptr) error(__FUNCTION__, "the --grid_* options need --grid_out FILE!");
+  if (*ga->out == 0) error(__FUNCTION__, "--grid_out needs a file name!");
+  ngsld_grid_params &p = ga->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.linked_min = 0.5;
+  p.abs_value = ga->is_signed ? 0 : 1;
+  if (ga->bin_size == nullptr) error(__FUNCTION__, "--grid_out needs the window in bp: --grid_bin_size INT!");
+  if (!parse_position(ga->bin_size, &p.bin_size) || p.bin_size < 1 || p.bin_size >= (1ull << 31))
+    error(__FUNCTION__, "--grid_bin_size must be an integer in [1, 2147483647]!");
+  if (ga->ld && (p.fields = parse_ld_list(ga->ld)) == 0)
+    error(__FUNCTION__, "--grid_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+  if (ga->max_kb_dist && (!parse_double(ga->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
+    error(__FUNCTION__, "--grid_max_kb_dist must be a number >= 0 (or inf)!");
+  if (ga->min_maf && (!parse_double(ga->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
+    error(__FUNCTION__, "--grid_min_maf must be a number >= 0!");
+  if (ga->linked_min && !parse_double(ga->linked_min, &p.linked_min)) error(__FUNCTION__, "--grid_linked_min must be a number!");
+  if (pars.in_pos == nullptr) error(__FUNCTION__, "--grid_out needs positions: it cannot run without --pos!");
+  if (pars.devices.size() > 1) error(__FUNCTION__, "--grid_out runs on one device: it cannot be combined with --devices!");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -562,6 +604,54 @@ void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos 
   if (pars.verbose >= 1)
     fprintf(stderr, "==> Site LD: %lu of %lu sites in %lu of %lu pairs\n", (unsigned long)st.sites_with_pairs, (unsigned long)n,
             (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
+}
+
+// one line per cell with rows, by chromosome (file order), bin1, bin2: the chromosome, the lower breaks b * B of the two
+// windows, the counted rows, then sum, mean, max and linked of every chosen statistic -- the long form geom_tile and image read
+void run_grid(ngsld_ctx *ctx, const Params &pars, GridArgs &ga, const ngsld_pos *pos) {
+  std::vector<const char *> lab(pars.n_sites);
+  for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  ngsld_grid_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_grid(ctx, &ga.p, lab.data(), &st) != NGSLD_OK) error("ngsld_grid", ngsld_last_error(ctx));
+  const uint64_t n = st.cells, B = ga.p.bin_size;
+  std::vector<int> fields;
+  for (int k = 0; k < 4; ++k)
+    if ((ga.p.fields >> k) & 1u) fields.push_back(k);
+  const size_t nf = fields.size();
+  uint64_t n_chr = 0;
+  if (ngsld_grid_chromosomes(ctx, 0, nullptr, &n_chr) != NGSLD_OK) error("ngsld_grid_chromosomes", ngsld_last_error(ctx));
+  std::vector<const char *> chr_name(n_chr);
+  if (ngsld_grid_chromosomes(ctx, n_chr, chr_name.data(), nullptr) != NGSLD_OK) error("ngsld_grid_chromosomes", ngsld_last_error(ctx));
+  std::vector<uint32_t> chr(n);
+  std::vector<uint64_t> b1(n), b2(n), rows(n), linked(nf * n);
+  std::vector<int64_t> sum(nf * n), top(nf * n);
+  std::vector<double> mean(nf * n);
+  if (ngsld_grid_cells(ctx, n, chr.data(), b1.data(), b2.data(), rows.data(), nullptr) != NGSLD_OK)
+    error("ngsld_grid_cells", ngsld_last_error(ctx));
+  for (size_t v = 0; v < nf; ++v)
+    if (ngsld_grid_get(ctx, 4 + fields[v], n, sum.data() + v * n, top.data() + v * n, linked.data() + v * n, mean.data() + v * n) !=
+        NGSLD_OK)
+      error("ngsld_grid_get", ngsld_last_error(ctx));
+  FILE *f = fopen(ga.out, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open LD grid output file!");
+  fprintf(f, "chr\tbin1\tbin2\tn");
+  for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
+  fprintf(f, "\n");
+  for (uint64_t i = 0; i < n; ++i) {
+    fprintf(f, "%s\t%lu\t%lu\t%lu", chr_name[chr[i]], (unsigned long)(b1[i] * B), (unsigned long)(b2[i] * B), (unsigned long)rows[i]);
+    for (size_t v = 0; v < nf; ++v) {
+      print_micro(f, sum[v * n + i]);
+      fprintf(f, "\t%.17g", mean[v * n + i]);
+      print_micro(f, top[v * n + i]);
+      fprintf(f, "\t%lu", (unsigned long)linked[v * n + i]);
+    }
+    fprintf(f, "\n");
+  }
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD grid output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD grid: %lu cells (%lu bins, a band of %lu) from %lu of %lu pairs\n", (unsigned long)n, (unsigned long)st.bins,
+            (unsigned long)st.band, (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
 }
 
 // --cluster_out: one line per site of the input, in file order, its cluster or NA; --cluster_table: one line per cluster of
@@ -1117,14 +1207,17 @@ int main(int argc, char **argv) {
   take_site_args(&argc, argv, &site);
   ClusterArgs cluster;
   take_cluster_args(&argc, argv, &cluster);
+  GridArgs grid;
+  take_grid_args(&argc, argv, &grid);
   parse_cmd_args(&pars, argc, argv);
   check_prune_args(pars, &prune);
   check_decay_args(pars, &decay);
   check_blocks_args(pars, &blocks);
   check_site_args(pars, &site);
   check_cluster_args(pars, &cluster);
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table without --out: no TSV
-  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given || cluster.given) || pars.out != NULL;
+  check_grid_args(pars, &grid);
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out without --out: no TSV
+  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given || cluster.given || grid.given) || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -1254,7 +1347,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given &&  // (the clusters need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given &&  // (the clusters and the grid need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the
@@ -1272,6 +1365,8 @@ int main(int argc, char **argv) {
     error(__FUNCTION__, "--site_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0 && cluster.given)
     error(__FUNCTION__, "--cluster_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  if (slab_sites > 0 && grid.given)
+    error(__FUNCTION__, "--grid_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -1429,6 +1524,10 @@ int main(int argc, char **argv) {
   if (cluster.given) {  // (a pass of the pair kernels of its own)
     run_clusters(ctx, pars, cluster, pos);
     timing_report.mark("LD clusters");
+  }
+  if (grid.given) {  // (a pass of the pair kernels of its own)
+    run_grid(ctx, pars, grid, pos);
+    timing_report.mark("LD grid");
   }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)

@@ -474,6 +474,19 @@ struct ngsld_ctx {
   } clusters;
   void clear_clusters() { clusters = Clusters(); }
 
+  // the cells of the last ngsld_grid (grid.hip), until the next ngsld_grid, ngsld_plan or ngsld_set_* (cleared with the block
+  // matrices): the chromosomes in file order, then per cell with rows -- by chromosome, b1, b2 -- its chromosome, bins and rows,
+  // and per chosen field [rank][cell] the sum and the maximum in micro-units, the linked rows and the mean
+  struct Grid {
+    uint32_t fields = 0;
+    std::vector<std::string> chr_name;
+    std::vector<uint32_t> chr;
+    std::vector<uint64_t> b1, b2, n, linked;
+    std::vector<int64_t> sum, max;
+    std::vector<double> mean;
+  } grid;
+  void clear_grid() { grid = Grid(); }
+
   // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
   // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
   uint32_t blocks_fields = 0;
@@ -488,6 +501,7 @@ struct ngsld_ctx {
   void clear_blocks() {  // (every ngsld_plan and ngsld_set_* comes through here)
     clear_sites();
     clear_clusters();
+    clear_grid();
     blocks_fields = 0;
     blocks_members = 0;
     d_blocks_val.release();
@@ -572,7 +586,8 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
 // host writer adds the gaps one by one.
 bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc);
 
-// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip), ngsld_site_ld (site_ld.hip) and ngsld_clusters (cluster.hip) read the records of
+// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip), ngsld_site_ld (site_ld.hip),
+// ngsld_clusters (cluster.hip) and ngsld_grid (grid.hip) read the records of
 // rows chunk by chunk and run a kernel of their own over each chunk's items (ld_records.h) ----
 // records of one chunk of rows (32 B each)
 constexpr uint64_t kRecordChunkPairs = 1ull << 24;

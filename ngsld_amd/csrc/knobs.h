@@ -15,7 +15,7 @@
 //   TEXT_GROUPS, TEXT_GROUP_PAIRS,
 //   EXACT_CHUNK_SITES, EXACT_SLOW_US, EXACT_STORE_NO_ROOM, REPLAY_LIST_CAP, REPLAY_SOURCE, LANE_ITER_CAP,
 //   PRUNE_HOST_AFTER, DECAY_LDS_BYTES, DECAY_CHUNK_PAIRS, BLOCKS_CHUNK_PAIRS, BLOCKS_HOST_ROWS, BLOCKS_TEXT_ROWS,
-//   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS
+//   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS, GRID_LDS_BYTES, GRID_CHUNK_PAIRS
 // (The knobs of closed A/B experiments -- lane caps and waves, sort-key tilings, run lengths, tile rows, text batch sizes -- are
 // gone; their measurements are in HISTORY.md.)
 #pragma once

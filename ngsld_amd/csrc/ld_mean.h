@@ -1,5 +1,5 @@
 // ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
-// (site_ld.hip) and of ngsld_clusters' clusters (cluster.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
+// (site_ld.hip), of ngsld_clusters' clusters (cluster.hip) and of ngsld_grid's cells (grid.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
 // compiles it alone.
 #pragma once
 
@@ -31,6 +31,16 @@ inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
   sticky = sticky || (low & 1);
   if ((low & 2) && (sticky || (m & 1))) ++m;
   return std::ldexp((double)m, 2 - sh);
+}
+
+// the double nearest to sum / (10^6 * rows): the mean of `rows` printed values whose micro-units add up to `sum` (ngsld_grid's
+// cells, grid.hip: up to a million of them a field).  Where sum < 2^53 and rows < 2^33 both operands are doubles, and one IEEE
+// division is that one rounding: the operands are exact, and a quotient of two integers below 2^53 never lies on a tie between
+// two doubles (a tie has 54 significant bits, hence a numerator of at least 2^53).  Elsewhere the long division.
+// tests/test_mean_nearest.py holds both branches to the exact quotient; GRID.md has what the short one saves.
+inline double mean_nearest(uint64_t sum, uint64_t rows) {
+  if (sum < (1ull << 53) && rows < (1ull << 33)) return (double)sum / (double)(rows * 1000000u);
+  return div_nearest((unsigned __int128)sum, (unsigned __int128)rows * 1000000u);
 }
 
 }  // namespace eng
