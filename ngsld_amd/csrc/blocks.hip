@@ -3,9 +3,9 @@
 // they are copied out or written as text.  BLOCKS.md has the rule, the deviations and why a cell's text is the TSV's.
 //
 //   members  host: each label's CHR:pos (up to the first TAB), the region's sites, their order by position (ord, -1 elsewhere)
-//   pairs    run_record_chunks over the member rows (an in-region pair has a member as s1): replayed pairs carry their
+//   pairs    RecordPass (record_pass.h) over the member rows (an in-region pair has a member as s1): replayed pairs carry their
 //            replayed values, the rows of other sites are not run
-//   scatter  one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the record's
+//   scatter  one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: the record's
 //            double bits of every chosen field to M_f[ord(s1) * n + ord(s2)], a presence byte to P[...] -- pairs are unique,
 //            no atomics; in file order = position order the lanes of an item write consecutive columns of one row
 //   sites    members with a pair in their row or column: one pass over P (lanes over columns), compacted by hipCUB
@@ -18,7 +18,7 @@
 #include "../../include/ngsld_host.h"
 #include "engine.h"
 #include "ld_fmt.h"
-#include "ld_records.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -186,12 +186,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t *P, const uns
   }
 }
 
-// the label's part up to its first TAB (a pos file with extra columns puts them behind one)
-std::string label_key(const char *l) {
-  const char *t = std::strchr(l, '\t');
-  return t ? std::string(l, t) : std::string(l);
-}
-
 // rank of TSV column `field` (4..7) among the chosen fields, -1 when it was not chosen
 int field_rank(uint32_t fields, int field) {
   if (field < 4 || field > 7 || !((fields >> (field - 4)) & 1u)) return -1;
@@ -213,11 +207,8 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   if (!(p->start < p->end)) return fail(c, NGSLD_ERR_INVALID, "start position must be smaller than end position.");
   if (labels == nullptr) return fail(c, NGSLD_ERR_INVALID, "LD blocks need positions: the labels are NULL");
   const uint64_t n_sites = c->n_sites;
-  if (n_sites >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
   ngsld_blocks_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
+  if (const int rc = begin_pass(c, S)) return rc;
   hipStream_t st = c->stream;
   int field[4] = {0, 0, 0, 0};
   const int ns = field_list(p->fields, field);
@@ -231,15 +222,11 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   std::vector<uint8_t> is_member(n_sites, 0);
   for (uint64_t s = 0; s < n_sites; ++s) {
     if (labels[s] == nullptr) return fail(c, NGSLD_ERR_INVALID, "a label is NULL");
-    const std::string key = label_key(labels[s]);
-    if (key == "(null)") return fail(c, NGSLD_ERR_INVALID, "LD blocks need positions: a label is \"(null)\"");
-    const size_t colon = key.find(':');
-    if (key.substr(0, colon) != chr) continue;
-    const std::string num = colon == std::string::npos ? std::string() : key.substr(colon + 1);
-    bool digits = !num.empty() && num.size() <= 19;
-    for (char ch : num) digits = digits && ch >= '0' && ch <= '9';
-    if (!digits) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD blocks: the position of label \"" + key + "\" is not plain decimal digits");
-    const uint64_t pos = std::strtoull(num.c_str(), nullptr, 10);
+    const LabelPos L = label_pos(labels[s]);
+    if (L.key == "(null)") return fail(c, NGSLD_ERR_INVALID, "LD blocks need positions: a label is \"(null)\"");
+    if (!L.on(chr)) continue;
+    uint64_t pos = 0;
+    if (!L.position(&pos)) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD blocks: the position of label \"" + L.key + "\" is not plain decimal digits");
     if (pos < p->start || pos > p->end) continue;
     mem.push_back({pos, s});
     is_member[s] = 1;
@@ -247,8 +234,8 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
   std::sort(mem.begin(), mem.end(), [](const Member &a, const Member &b) { return a.pos < b.pos || (a.pos == b.pos && a.site < b.site); });
   for (size_t k = 1; k < mem.size(); ++k)
     if (mem[k].pos == mem[k - 1].pos)
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "LD blocks: sites \"" + label_key(labels[mem[k - 1].site]) + "\" and \"" +
-                                                label_key(labels[mem[k].site]) + "\" of the region share a position");
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "LD blocks: sites \"" + label_pos(labels[mem[k - 1].site]).key + "\" and \"" +
+                                                label_pos(labels[mem[k].site]).key + "\" of the region share a position");
   const uint64_t n = mem.size();
   S.members = n;
   const uint64_t bytes = (uint64_t)ns * n * n * 8 + n * n;
@@ -273,14 +260,11 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, c->d_blocks_present.resize((size_t)n * n));
     HIP_TRY(c, hipMemsetAsync(c->d_blocks_present.p, 0, n * n, st));
     HIP_TRY(c, hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
-    const uint64_t chunk = record_chunk(test_knob("BLOCKS_CHUNK_PAIRS"));
-    const uint64_t rec_cap = record_cap(c, chunk, is_member.data());
-    DevBuf<ngsld_rec_std> d_rec;
-    HIP_TRY(c, d_rec.resize(rec_cap));
-    EventPair ev;
-    HIP_TRY(c, ev.create());
+    // the member rows only: the rows of other sites are not run
+    RecordPass R;
+    if (const int rc = R.open(c, record_chunk(test_knob("BLOCKS_CHUNK_PAIRS")), is_member.data())) return rc;
     ScatterArgs A{};
-    A.rec = d_rec.p;
+    A.rec = R.records();
     A.ord = d_ord.p;
     A.n = n;
     A.ns = ns;
@@ -289,16 +273,12 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     A.present = c->d_blocks_present.p;
     A.in_region = d_count.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    // the member rows only: the rows of other sites are not run
-    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
-      A.out_base = c->h_row_off[r0];
-      // (it returns once the launches are done: the next chunk's pairs overwrite the records)
-      return launch_record_items(c, ev, r0, r1, &S.scatter_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
-        A.items = items;
-        A.n_items = n_items;
-        hipLaunchKernelGGL(scatter_kernel, dim3(std::min<unsigned>(blocks_for(n_items * 64), max_blocks)), dim3(256), 0, st, A);
-      });
-    }, is_member.data());
+    const int rc = R.run(&S.pairs_ms, &S.scatter_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+      A.out_base = ch.out_base;
+      A.items = items;
+      A.n_items = n_items;
+      hipLaunchKernelGGL(scatter_kernel, dim3(std::min<unsigned>(blocks_for(n_items * 64), max_blocks)), dim3(256), 0, st, A);
+    });
     if (rc != NGSLD_OK) return rc;
 
     // ---- matrix sites: members with a pair in their row or column, compacted in matrix order ----
@@ -308,6 +288,8 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, d_col.resize(n));
     HIP_TRY(c, d_num.resize(1));
     HIP_TRY(c, hipMemsetAsync(d_mark.p, 0, n, st));
+    EventPair ev;
+    HIP_TRY(c, ev.create());
     HIP_TRY(c, hipEventRecord(ev.a, st));
     hipLaunchKernelGGL(sites_kernel, dim3(blocks_for(n), (unsigned)((n + kSiteBand - 1) / kSiteBand)), dim3(256), 0, st,
                        (const uint8_t *)c->d_blocks_present.p, n, d_mark.p);
@@ -335,7 +317,7 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
       for (uint32_t k = 0; k < m; ++k) {
         const uint64_t s = mem[col[k]].site;
         c->blocks_site.push_back(s);
-        c->blocks_label.push_back(label_key(labels[s]));
+        c->blocks_label.push_back(label_pos(labels[s]).key);
         off[k + 1] = off[k] + c->blocks_label.back().size();
       }
       std::string blob;

@@ -120,64 +120,7 @@ struct PruneArgs {
   bool keep_heavy = false;
   ngsld_prune_params p{};
   std::vector<std::string> subset;
-};
-
-// Takes the flags named prefix* (one or two dashes, "--name value" or "--name=value") out of argv: valued[k]'s value goes to
-// *dst[k], switch_name (may be null) is a flag without a value.  *given: any such flag.  The values are checked once the
-// reference's own arguments have been.
-void take_flags(int *argc, char **argv, const char *prefix, const char *const *valued, const char **const *dst, size_t n_valued,
-                const char *switch_name, bool *switch_on, bool *given) {
-  const size_t plen = std::strlen(prefix);
-  int w = 1;
-  for (int i = 1; i < *argc; ++i) {
-    const char *a = argv[i];
-    if (std::strcmp(a, "--") == 0) {  // (getopt's end of options: the rest is not ours)
-      while (i < *argc) argv[w++] = argv[i++];
-      break;
-    }
-    const char *name = a[0] == '-' ? (a[1] == '-' ? a + 2 : a + 1) : nullptr;
-    if (name == nullptr || std::strncmp(name, prefix, plen) != 0) {
-      argv[w++] = argv[i];
-      continue;
-    }
-    const char *eq = std::strchr(name, '=');
-    const std::string key = eq ? std::string(name, eq) : std::string(name);
-    *given = true;
-    if (switch_name != nullptr && key == switch_name && eq == nullptr) {
-      *switch_on = true;
-      continue;
-    }
-    bool known = false;
-    for (size_t k = 0; k < n_valued; ++k) {
-      if (key != valued[k]) continue;
-      known = true;
-      if (eq != nullptr) {
-        *dst[k] = eq + 1;
-      } else if (i + 1 < *argc) {
-        *dst[k] = argv[++i];
-      } else {
-        const std::string msg = "--" + key + " needs a value!";
-        error(__FUNCTION__, msg.c_str());
-      }
-    }
-    if (!known) {
-      const std::string msg = "unknown option --" + key + "!";
-      error(__FUNCTION__, msg.c_str());
-    }
-  }
-  argv[w] = nullptr;
-  *argc = w;
-}
-
-// The --prune_* flags out of argv; check_prune_args checks them.
-void take_prune_args(int *argc, char **argv, PruneArgs *pa) {
-  static const char *const kValued[] = {"prune_out", "prune_excl", "prune_subset", "prune_field", "prune_weight_type",
-                                        "prune_precision", "prune_max_kb_dist", "prune_min_weight"};
-  const char **const dst[] = {&pa->out, &pa->excl, &pa->subset_file, &pa->field, &pa->type, &pa->precision, &pa->max_kb_dist,
-                              &pa->min_weight};
-  take_flags(argc, argv, "prune_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "prune_keep_heavy", &pa->keep_heavy,
-             &pa->given);
-}
+} prune;
 
 // ---- --decay_* (new): LD decay bins and fit on the device ----
 struct DecayArgs {
@@ -186,28 +129,14 @@ struct DecayArgs {
   const char *n_ind = nullptr, *recomb_rate = nullptr;
   ngsld_decay_params p{};
   double n_ind_v = 0, recomb_rate_v = 1;
-};
-
-void take_decay_args(int *argc, char **argv, DecayArgs *da) {
-  static const char *const kValued[] = {"decay_out", "decay_fit", "decay_ld", "decay_bin_size", "decay_max_kb_dist",
-                                        "decay_min_maf", "decay_n_ind", "decay_recomb_rate"};
-  const char **const dst[] = {&da->out, &da->fit, &da->ld, &da->bin_size, &da->max_kb_dist, &da->min_maf, &da->n_ind,
-                              &da->recomb_rate};
-  take_flags(argc, argv, "decay_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &da->given);
-}
+} decay;
 
 // ---- --blocks_* (new): LD block matrices of one region on the device ----
 struct BlocksArgs {
   bool given = false;  // any --blocks_* flag
   const char *out = nullptr, *chr = nullptr, *start = nullptr, *end = nullptr, *ld = nullptr;
   ngsld_blocks_params p{};
-};
-
-void take_blocks_args(int *argc, char **argv, BlocksArgs *ba) {
-  static const char *const kValued[] = {"blocks_out", "blocks_chr", "blocks_start", "blocks_end", "blocks_ld"};
-  const char **const dst[] = {&ba->out, &ba->chr, &ba->start, &ba->end, &ba->ld};
-  take_flags(argc, argv, "blocks_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), nullptr, nullptr, &ba->given);
-}
+} blocks;
 
 // ---- --site_* (new): per-site LD summaries on the device ----
 struct SiteArgs {
@@ -215,13 +144,7 @@ struct SiteArgs {
   const char *out = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
   bool is_signed = false;
   ngsld_site_ld_params p{};
-};
-
-void take_site_args(int *argc, char **argv, SiteArgs *sa) {
-  static const char *const kValued[] = {"site_out", "site_ld", "site_max_kb_dist", "site_min_maf", "site_linked_min"};
-  const char **const dst[] = {&sa->out, &sa->ld, &sa->max_kb_dist, &sa->min_maf, &sa->linked_min};
-  take_flags(argc, argv, "site_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "site_signed", &sa->is_signed, &sa->given);
-}
+} site;
 
 // ---- --cluster_* (new): LD clusters on the device ----
 struct ClusterArgs {
@@ -231,14 +154,7 @@ struct ClusterArgs {
   bool is_signed = false;
   uint64_t min_size_v = 2;
   ngsld_clusters_params p{};
-};
-
-void take_cluster_args(int *argc, char **argv, ClusterArgs *ca) {
-  static const char *const kValued[] = {"cluster_out", "cluster_table", "cluster_field", "cluster_min_weight", "cluster_max_kb_dist",
-                                        "cluster_min_maf", "cluster_min_size"};
-  const char **const dst[] = {&ca->out, &ca->table, &ca->field, &ca->min_weight, &ca->max_kb_dist, &ca->min_maf, &ca->min_size};
-  take_flags(argc, argv, "cluster_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "cluster_signed", &ca->is_signed, &ca->given);
-}
+} cluster;
 
 // ---- --grid_* (new): the LD grid on the device ----
 struct GridArgs {
@@ -246,13 +162,7 @@ struct GridArgs {
   const char *out = nullptr, *bin_size = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
   bool is_signed = false;
   ngsld_grid_params p{};
-};
-
-void take_grid_args(int *argc, char **argv, GridArgs *ga) {
-  static const char *const kValued[] = {"grid_out", "grid_bin_size", "grid_ld", "grid_max_kb_dist", "grid_min_maf", "grid_linked_min"};
-  const char **const dst[] = {&ga->out, &ga->bin_size, &ga->ld, &ga->max_kb_dist, &ga->min_maf, &ga->linked_min};
-  take_flags(argc, argv, "grid_", kValued, dst, sizeof(kValued) / sizeof(kValued[0]), "grid_signed", &ga->is_signed, &ga->given);
-}
+} grid;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -261,8 +171,39 @@ bool parse_double(const char *txt, double *out) {
   return *end == 0 && !std::isnan(*out);
 }
 
-void check_prune_args(const Params &pars, PruneArgs *pa) {
-  if (!pa->given) return;
+// The values several families take: flag is the option as the user writes it ("--site_min_maf"), func the checker the ERROR
+// block names; a flag that was not given (txt null) leaves *out alone.
+[[noreturn]] void bad_value(const char *func, const char *flag, const char *must) {
+  const std::string msg = std::string(flag) + must;
+  error(func, msg.c_str());
+}
+// a number (nan is none)
+void number_arg(const char *func, const char *flag, const char *txt, double *out) {
+  if (txt && !parse_double(txt, out)) bad_value(func, flag, " must be a number!");
+}
+// a number >= 0 or inf: *_max_kb_dist
+void dist_arg(const char *func, const char *flag, const char *txt, double *out) {
+  if (txt && (!parse_double(txt, out) || *out < 0)) bad_value(func, flag, " must be a number >= 0 (or inf)!");
+}
+// a finite number >= 0: *_min_maf, --decay_n_ind
+void finite_arg(const char *func, const char *flag, const char *txt, double *out) {
+  if (txt && (!parse_double(txt, out) || *out < 0 || std::isinf(*out))) bad_value(func, flag, " must be a number >= 0!");
+}
+// a TSV column 4..7: --prune_field, --cluster_field
+void column_arg(const char *func, const char *flag, const char *txt, int32_t *out) {
+  if (txt == nullptr) return;
+  char *end = nullptr;
+  const long f = strtol(txt, &end, 10);
+  if (*txt == 0 || *end != 0 || f < 4 || f > 7) bad_value(func, flag, " must be 4 (r2_ExpG), 5 (D), 6 (D') or 7 (r2)!");
+  *out = (int32_t)f;
+}
+// out_flag ("--site_out") runs on one device
+void one_device(const char *func, const Params &pars, const char *out_flag) {
+  if (pars.devices.size() > 1) bad_value(func, out_flag, " runs on one device: it cannot be combined with --devices!");
+}
+
+void check_prune_args(const Params &pars) {
+  PruneArgs *pa = &prune;
   if (pa->out == nullptr || *pa->out == 0) error(__FUNCTION__, "the --prune_* options need --prune_out FILE!");
   ngsld_prune_params &p = pa->p;
   p.struct_size = sizeof(p);
@@ -272,13 +213,7 @@ void check_prune_args(const Params &pars, PruneArgs *pa) {
   p.weight_type = 'a';
   p.precision = 4;
   p.keep_heavy = pa->keep_heavy ? 1 : 0;
-  if (pa->field) {
-    char *end = nullptr;
-    const long f = strtol(pa->field, &end, 10);
-    if (*pa->field == 0 || *end != 0 || f < 4 || f > 7)
-      error(__FUNCTION__, "--prune_field must be 4 (r2_ExpG), 5 (D), 6 (D') or 7 (r2)!");
-    p.field = (int32_t)f;
-  }
+  column_arg(__FUNCTION__, "--prune_field", pa->field, &p.field);
   if (pa->type) {
     if (std::strlen(pa->type) != 1 || std::strchr("aen", pa->type[0]) == nullptr)
       error(__FUNCTION__, "--prune_weight_type must be a, e or n!");
@@ -290,11 +225,10 @@ void check_prune_args(const Params &pars, PruneArgs *pa) {
     if (*pa->precision == 0 || *end != 0 || v < 0 || v > 15) error(__FUNCTION__, "--prune_precision must be an integer in [0,15]!");
     p.precision = (int32_t)v;
   }
-  if (pa->max_kb_dist && (!parse_double(pa->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
-    error(__FUNCTION__, "--prune_max_kb_dist must be a number >= 0 (or inf)!");
-  if (pa->min_weight && !parse_double(pa->min_weight, &p.min_weight)) error(__FUNCTION__, "--prune_min_weight must be a number!");
+  dist_arg(__FUNCTION__, "--prune_max_kb_dist", pa->max_kb_dist, &p.max_kb_dist);
+  number_arg(__FUNCTION__, "--prune_min_weight", pa->min_weight, &p.min_weight);
   if (pa->excl != nullptr && *pa->excl == 0) error(__FUNCTION__, "--prune_excl needs a file name!");
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--prune_out runs on one device: it cannot be combined with --devices!");
+  one_device(__FUNCTION__, pars, "--prune_out");
   if (pa->subset_file) {  // one label per line, plain or gzip-compressed (the script's IO::Zlib reads both)
     gzFile f = gzopen(pa->subset_file, "rb");
     if (f == nullptr) error(__FUNCTION__, "cannot open --prune_subset file!");
@@ -316,59 +250,7 @@ void check_prune_args(const Params &pars, PruneArgs *pa) {
 // the statistics of --decay_ld, in TSV column order (bit k = column 4 + k)
 const char *const kDecayFields[4] = {"r2_ExpG", "D", "Dp", "r2"};
 
-void check_decay_args(const Params &pars, DecayArgs *da) {
-  if (!da->given) return;
-  if (da->out == nullptr && da->fit == nullptr) error(__FUNCTION__, "the --decay_* options need --decay_out FILE or --decay_fit FILE!");
-  if (da->out != nullptr && *da->out == 0) error(__FUNCTION__, "--decay_out needs a file name!");
-  if (da->fit != nullptr && *da->fit == 0) error(__FUNCTION__, "--decay_fit needs a file name!");
-  ngsld_decay_params &p = da->p;
-  p.struct_size = sizeof(p);
-  p.fields = 8;  // r2
-  p.bin_size = 250;
-  p.max_kb_dist = INFINITY;
-  p.min_maf = 0;
-  if (da->ld) {
-    p.fields = 0;
-    const std::string txt = da->ld;
-    size_t b = 0;
-    while (true) {
-      const size_t e = std::min(txt.find(',', b), txt.size());
-      const std::string name = txt.substr(b, e - b);
-      int f = -1;
-      for (int k = 0; k < 4; ++k)
-        if (name == kDecayFields[k]) f = k;
-      if (f < 0) error(__FUNCTION__, "--decay_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
-      p.fields |= 1u << f;
-      if (e == txt.size()) break;
-      b = e + 1;
-    }
-  }
-  if (da->bin_size && (!parse_double(da->bin_size, &p.bin_size) || !(p.bin_size > 1) || std::isinf(p.bin_size)))
-    error(__FUNCTION__, "--decay_bin_size must be a number > 1!");
-  if (da->max_kb_dist && (!parse_double(da->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
-    error(__FUNCTION__, "--decay_max_kb_dist must be a number >= 0 (or inf)!");
-  if (da->min_maf && (!parse_double(da->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
-    error(__FUNCTION__, "--decay_min_maf must be a number >= 0!");
-  if (da->n_ind && (!parse_double(da->n_ind, &da->n_ind_v) || da->n_ind_v < 0 || std::isinf(da->n_ind_v)))
-    error(__FUNCTION__, "--decay_n_ind must be a number >= 0!");
-  if (da->recomb_rate && (!parse_double(da->recomb_rate, &da->recomb_rate_v) || !(da->recomb_rate_v > 0) || std::isinf(da->recomb_rate_v)))
-    error(__FUNCTION__, "--decay_recomb_rate must be a number > 0!");
-  if (da->n_ind_v > 0 && (p.fields & (1u | 8u)) == 0) error(__FUNCTION__, "--decay_n_ind is only used for the r2 and r2_ExpG fits!");
-  if (da->n_ind_v > 0 && da->fit != nullptr && (p.fields & 4u))
-    error(__FUNCTION__, "--decay_n_ind cannot be combined with a Dp fit!");
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--decay_out runs on one device: it cannot be combined with --devices!");
-}
-
-// a --blocks_start / --blocks_end value: plain decimal digits
-bool parse_position(const char *txt, uint64_t *out) {
-  if (txt == nullptr || *txt == 0 || std::strlen(txt) > 19) return false;
-  for (const char *q = txt; *q; ++q)
-    if (*q < '0' || *q > '9') return false;
-  *out = std::strtoull(txt, nullptr, 10);
-  return true;
-}
-
-// the statistics of a comma-separated list (--decay_ld, --blocks_ld, --site_ld) as a mask, bit k = column 4 + k; 0 when a name is unknown
+// the statistics of a comma-separated list (--decay_ld, --blocks_ld, --site_ld, --grid_ld) as a mask, bit k = column 4 + k; 0 when a name is unknown
 uint32_t parse_ld_list(const char *txt) {
   uint32_t fields = 0;
   const std::string s = txt;
@@ -386,8 +268,55 @@ uint32_t parse_ld_list(const char *txt) {
   }
 }
 
-void check_blocks_args(const Params &pars, BlocksArgs *ba) {
-  if (!ba->given) return;
+// ... into *fields, where the flag was given
+void ld_arg(const char *func, const char *flag, const char *txt, uint32_t *fields) {
+  if (txt && (*fields = parse_ld_list(txt)) == 0) bad_value(func, flag, " must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+}
+
+// the statistics of a mask, as indices into kDecayFields
+std::vector<int> fields_of(uint32_t mask) {
+  std::vector<int> fields;
+  for (int k = 0; k < 4; ++k)
+    if ((mask >> k) & 1u) fields.push_back(k);
+  return fields;
+}
+
+void check_decay_args(const Params &pars) {
+  DecayArgs *da = &decay;
+  if (da->out == nullptr && da->fit == nullptr) error(__FUNCTION__, "the --decay_* options need --decay_out FILE or --decay_fit FILE!");
+  if (da->out != nullptr && *da->out == 0) error(__FUNCTION__, "--decay_out needs a file name!");
+  if (da->fit != nullptr && *da->fit == 0) error(__FUNCTION__, "--decay_fit needs a file name!");
+  ngsld_decay_params &p = da->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.bin_size = 250;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  ld_arg(__FUNCTION__, "--decay_ld", da->ld, &p.fields);
+  if (da->bin_size && (!parse_double(da->bin_size, &p.bin_size) || !(p.bin_size > 1) || std::isinf(p.bin_size)))
+    error(__FUNCTION__, "--decay_bin_size must be a number > 1!");
+  dist_arg(__FUNCTION__, "--decay_max_kb_dist", da->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--decay_min_maf", da->min_maf, &p.min_maf);
+  finite_arg(__FUNCTION__, "--decay_n_ind", da->n_ind, &da->n_ind_v);
+  if (da->recomb_rate && (!parse_double(da->recomb_rate, &da->recomb_rate_v) || !(da->recomb_rate_v > 0) || std::isinf(da->recomb_rate_v)))
+    error(__FUNCTION__, "--decay_recomb_rate must be a number > 0!");
+  if (da->n_ind_v > 0 && (p.fields & (1u | 8u)) == 0) error(__FUNCTION__, "--decay_n_ind is only used for the r2 and r2_ExpG fits!");
+  if (da->n_ind_v > 0 && da->fit != nullptr && (p.fields & 4u))
+    error(__FUNCTION__, "--decay_n_ind cannot be combined with a Dp fit!");
+  one_device(__FUNCTION__, pars, "--decay_out");
+}
+
+// a --blocks_start / --blocks_end value: plain decimal digits
+bool parse_position(const char *txt, uint64_t *out) {
+  if (txt == nullptr || *txt == 0 || std::strlen(txt) > 19) return false;
+  for (const char *q = txt; *q; ++q)
+    if (*q < '0' || *q > '9') return false;
+  *out = std::strtoull(txt, nullptr, 10);
+  return true;
+}
+
+void check_blocks_args(const Params &pars) {
+  BlocksArgs *ba = &blocks;
   if (ba->out == nullptr) error(__FUNCTION__, "the --blocks_* options need --blocks_out PREFIX!");
   if (*ba->out == 0) error(__FUNCTION__, "--blocks_out needs a file name prefix!");
   ngsld_blocks_params &p = ba->p;
@@ -400,14 +329,13 @@ void check_blocks_args(const Params &pars, BlocksArgs *ba) {
   if (!parse_position(ba->start, &p.start)) error(__FUNCTION__, "--blocks_start must be a non-negative integer!");
   if (!parse_position(ba->end, &p.end)) error(__FUNCTION__, "--blocks_end must be a non-negative integer!");
   if (p.start >= p.end) error(__FUNCTION__, "start position must be smaller than end position.");
-  if (ba->ld && (p.fields = parse_ld_list(ba->ld)) == 0)
-    error(__FUNCTION__, "--blocks_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
+  ld_arg(__FUNCTION__, "--blocks_ld", ba->ld, &p.fields);
   if (pars.in_pos == nullptr) error(__FUNCTION__, "--blocks_out needs positions: it cannot run without --pos!");
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--blocks_out runs on one device: it cannot be combined with --devices!");
+  one_device(__FUNCTION__, pars, "--blocks_out");
 }
 
-void check_site_args(const Params &pars, SiteArgs *sa) {
-  if (!sa->given) return;
+void check_site_args(const Params &pars) {
+  SiteArgs *sa = &site;
   if (sa->out == nullptr) error(__FUNCTION__, "the --site_* options need --site_out FILE!");
   if (*sa->out == 0) error(__FUNCTION__, "--site_out needs a file name!");
   ngsld_site_ld_params &p = sa->p;
@@ -417,18 +345,15 @@ void check_site_args(const Params &pars, SiteArgs *sa) {
   p.min_maf = 0;
   p.linked_min = 0.5;
   p.abs_value = sa->is_signed ? 0 : 1;
-  if (sa->ld && (p.fields = parse_ld_list(sa->ld)) == 0)
-    error(__FUNCTION__, "--site_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
-  if (sa->max_kb_dist && (!parse_double(sa->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
-    error(__FUNCTION__, "--site_max_kb_dist must be a number >= 0 (or inf)!");
-  if (sa->min_maf && (!parse_double(sa->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
-    error(__FUNCTION__, "--site_min_maf must be a number >= 0!");
-  if (sa->linked_min && !parse_double(sa->linked_min, &p.linked_min)) error(__FUNCTION__, "--site_linked_min must be a number!");
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--site_out runs on one device: it cannot be combined with --devices!");
+  ld_arg(__FUNCTION__, "--site_ld", sa->ld, &p.fields);
+  dist_arg(__FUNCTION__, "--site_max_kb_dist", sa->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--site_min_maf", sa->min_maf, &p.min_maf);
+  number_arg(__FUNCTION__, "--site_linked_min", sa->linked_min, &p.linked_min);
+  one_device(__FUNCTION__, pars, "--site_out");
 }
 
-void check_cluster_args(const Params &pars, ClusterArgs *ca) {
-  if (!ca->given) return;
+void check_cluster_args(const Params &pars) {
+  ClusterArgs *ca = &cluster;
   if (ca->out == nullptr && ca->table == nullptr)
     error(__FUNCTION__, "the --cluster_* options need --cluster_out FILE or --cluster_table FILE!");
   if (ca->out != nullptr && *ca->out == 0) error(__FUNCTION__, "--cluster_out needs a file name!");
@@ -440,18 +365,10 @@ void check_cluster_args(const Params &pars, ClusterArgs *ca) {
   p.min_maf = 0;
   p.min_weight = 0.5;
   p.abs_value = ca->is_signed ? 0 : 1;
-  if (ca->field) {
-    char *end = nullptr;
-    const long f = strtol(ca->field, &end, 10);
-    if (*ca->field == 0 || *end != 0 || f < 4 || f > 7)
-      error(__FUNCTION__, "--cluster_field must be 4 (r2_ExpG), 5 (D), 6 (D') or 7 (r2)!");
-    p.field = (int32_t)f;
-  }
-  if (ca->min_weight && !parse_double(ca->min_weight, &p.min_weight)) error(__FUNCTION__, "--cluster_min_weight must be a number!");
-  if (ca->max_kb_dist && (!parse_double(ca->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
-    error(__FUNCTION__, "--cluster_max_kb_dist must be a number >= 0 (or inf)!");
-  if (ca->min_maf && (!parse_double(ca->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
-    error(__FUNCTION__, "--cluster_min_maf must be a number >= 0!");
+  column_arg(__FUNCTION__, "--cluster_field", ca->field, &p.field);
+  number_arg(__FUNCTION__, "--cluster_min_weight", ca->min_weight, &p.min_weight);
+  dist_arg(__FUNCTION__, "--cluster_max_kb_dist", ca->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--cluster_min_maf", ca->min_maf, &p.min_maf);
   if (ca->min_size) {
     char *end = nullptr;
     const bool digits = *ca->min_size >= '0' && *ca->min_size <= '9';
@@ -459,11 +376,11 @@ void check_cluster_args(const Params &pars, ClusterArgs *ca) {
     if (!digits || *end != 0 || v < 1 || v > 0xffffffffull) error(__FUNCTION__, "--cluster_min_size must be an integer >= 1!");
     ca->min_size_v = v;
   }
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--cluster_out runs on one device: it cannot be combined with --devices!");
+  one_device(__FUNCTION__, pars, "--cluster_out");
 }
 
-void check_grid_args(const Params &pars, GridArgs *ga) {
-  if (!ga->given) return;
+void check_grid_args(const Params &pars) {
+  GridArgs *ga = &grid;
   if (ga->out == nullptr) error(__FUNCTION__, "the --grid_* options need --grid_out FILE!");
   if (*ga->out == 0) error(__FUNCTION__, "--grid_out needs a file name!");
   ngsld_grid_params &p = ga->p;
@@ -476,15 +393,12 @@ void check_grid_args(const Params &pars, GridArgs *ga) {
   if (ga->bin_size == nullptr) error(__FUNCTION__, "--grid_out needs the window in bp: --grid_bin_size INT!");
   if (!parse_position(ga->bin_size, &p.bin_size) || p.bin_size < 1 || p.bin_size >= (1ull << 31))
     error(__FUNCTION__, "--grid_bin_size must be an integer in [1, 2147483647]!");
-  if (ga->ld && (p.fields = parse_ld_list(ga->ld)) == 0)
-    error(__FUNCTION__, "--grid_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!");
-  if (ga->max_kb_dist && (!parse_double(ga->max_kb_dist, &p.max_kb_dist) || p.max_kb_dist < 0))
-    error(__FUNCTION__, "--grid_max_kb_dist must be a number >= 0 (or inf)!");
-  if (ga->min_maf && (!parse_double(ga->min_maf, &p.min_maf) || p.min_maf < 0 || std::isinf(p.min_maf)))
-    error(__FUNCTION__, "--grid_min_maf must be a number >= 0!");
-  if (ga->linked_min && !parse_double(ga->linked_min, &p.linked_min)) error(__FUNCTION__, "--grid_linked_min must be a number!");
+  ld_arg(__FUNCTION__, "--grid_ld", ga->ld, &p.fields);
+  dist_arg(__FUNCTION__, "--grid_max_kb_dist", ga->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--grid_min_maf", ga->min_maf, &p.min_maf);
+  number_arg(__FUNCTION__, "--grid_linked_min", ga->linked_min, &p.linked_min);
   if (pars.in_pos == nullptr) error(__FUNCTION__, "--grid_out needs positions: it cannot run without --pos!");
-  if (pars.devices.size() > 1) error(__FUNCTION__, "--grid_out runs on one device: it cannot be combined with --devices!");
+  one_device(__FUNCTION__, pars, "--grid_out");
 }
 
 FILE *open_or_die(const char *path) {
@@ -493,13 +407,12 @@ FILE *open_or_die(const char *path) {
   return f;
 }
 
-void run_decay(ngsld_ctx *ctx, const Params &pars, DecayArgs &da) {
+void run_decay(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
+  DecayArgs &da = decay;
   ngsld_decay_stats st{};
   st.struct_size = sizeof(st);
   if (ngsld_decay(ctx, &da.p, &st) != NGSLD_OK) error("ngsld_decay", ngsld_last_error(ctx));
-  std::vector<int> fields;
-  for (int k = 0; k < 4; ++k)
-    if ((da.p.fields >> k) & 1u) fields.push_back(k);
+  const std::vector<int> fields = fields_of(da.p.fields);
   const size_t nf = fields.size();
   const uint64_t nb = st.bins;
   std::vector<double> dist(nb), mean(nb * nf);
@@ -562,16 +475,36 @@ void print_site(FILE *f, const ngsld_pos *pos, uint64_t s) {
   }
 }
 
+// The summaries --site_out and --grid_out write after a line's own columns: sum, mean, max and linked of every chosen statistic.
+void print_summary_header(FILE *f, const std::vector<int> &fields) {
+  for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
+  fprintf(f, "\n");
+}
+// entry i of n, which has `rows` rows (the arrays hold one statistic after the other); NA for the mean and max of no rows
+void print_summaries(FILE *f, size_t nf, uint64_t n, uint64_t i, uint64_t rows, const int64_t *sum, const double *mean, const int64_t *top,
+                     const uint64_t *linked) {
+  for (size_t v = 0; v < nf; ++v) {
+    print_micro(f, sum[v * n + i]);
+    if (rows == 0) {
+      fprintf(f, "\tNA\tNA");
+    } else {
+      fprintf(f, "\t%.17g", mean[v * n + i]);
+      print_micro(f, top[v * n + i]);
+    }
+    fprintf(f, "\t%lu", (unsigned long)linked[v * n + i]);
+  }
+  fprintf(f, "\n");
+}
+
 // one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the
 // counted rows, then sum, mean, max and linked of every chosen statistic; NA for the mean and max of a site without rows
-void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos *pos) {
+void run_site(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  SiteArgs &sa = site;
   ngsld_site_ld_stats st{};
   st.struct_size = sizeof(st);
   if (ngsld_site_ld(ctx, &sa.p, &st) != NGSLD_OK) error("ngsld_site_ld", ngsld_last_error(ctx));
   const uint64_t n = pars.n_sites;
-  std::vector<int> fields;
-  for (int k = 0; k < 4; ++k)
-    if ((sa.p.fields >> k) & 1u) fields.push_back(k);
+  const std::vector<int> fields = fields_of(sa.p.fields);
   const size_t nf = fields.size();
   std::vector<uint64_t> rows(n), linked(nf * n);
   std::vector<int64_t> sum(nf * n), top(nf * n);
@@ -583,22 +516,11 @@ void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos 
   FILE *f = fopen(sa.out, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open site LD output file!");
   fprintf(f, "site\tn");
-  for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
-  fprintf(f, "\n");
+  print_summary_header(f, fields);
   for (uint64_t s = 0; s < n; ++s) {
     print_site(f, pos, s);
     fprintf(f, "\t%lu", (unsigned long)rows[s]);
-    for (size_t v = 0; v < nf; ++v) {
-      print_micro(f, sum[v * n + s]);
-      if (rows[s] == 0) {
-        fprintf(f, "\tNA\tNA");
-      } else {
-        fprintf(f, "\t%.17g", mean[v * n + s]);
-        print_micro(f, top[v * n + s]);
-      }
-      fprintf(f, "\t%lu", (unsigned long)linked[v * n + s]);
-    }
-    fprintf(f, "\n");
+    print_summaries(f, nf, n, s, rows[s], sum.data(), mean.data(), top.data(), linked.data());
   }
   if (fclose(f) != 0) error(__FUNCTION__, "cannot write site LD output file!");
   if (pars.verbose >= 1)
@@ -608,16 +530,15 @@ void run_site(ngsld_ctx *ctx, const Params &pars, SiteArgs &sa, const ngsld_pos 
 
 // one line per cell with rows, by chromosome (file order), bin1, bin2: the chromosome, the lower breaks b * B of the two
 // windows, the counted rows, then sum, mean, max and linked of every chosen statistic -- the long form geom_tile and image read
-void run_grid(ngsld_ctx *ctx, const Params &pars, GridArgs &ga, const ngsld_pos *pos) {
+void run_grid(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  GridArgs &ga = grid;
   std::vector<const char *> lab(pars.n_sites);
   for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
   ngsld_grid_stats st{};
   st.struct_size = sizeof(st);
   if (ngsld_grid(ctx, &ga.p, lab.data(), &st) != NGSLD_OK) error("ngsld_grid", ngsld_last_error(ctx));
   const uint64_t n = st.cells, B = ga.p.bin_size;
-  std::vector<int> fields;
-  for (int k = 0; k < 4; ++k)
-    if ((ga.p.fields >> k) & 1u) fields.push_back(k);
+  const std::vector<int> fields = fields_of(ga.p.fields);
   const size_t nf = fields.size();
   uint64_t n_chr = 0;
   if (ngsld_grid_chromosomes(ctx, 0, nullptr, &n_chr) != NGSLD_OK) error("ngsld_grid_chromosomes", ngsld_last_error(ctx));
@@ -636,17 +557,10 @@ void run_grid(ngsld_ctx *ctx, const Params &pars, GridArgs &ga, const ngsld_pos 
   FILE *f = fopen(ga.out, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD grid output file!");
   fprintf(f, "chr\tbin1\tbin2\tn");
-  for (int k : fields) fprintf(f, "\tsum_%s\tmean_%s\tmax_%s\tlinked_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k]);
-  fprintf(f, "\n");
+  print_summary_header(f, fields);
   for (uint64_t i = 0; i < n; ++i) {
     fprintf(f, "%s\t%lu\t%lu\t%lu", chr_name[chr[i]], (unsigned long)(b1[i] * B), (unsigned long)(b2[i] * B), (unsigned long)rows[i]);
-    for (size_t v = 0; v < nf; ++v) {
-      print_micro(f, sum[v * n + i]);
-      fprintf(f, "\t%.17g", mean[v * n + i]);
-      print_micro(f, top[v * n + i]);
-      fprintf(f, "\t%lu", (unsigned long)linked[v * n + i]);
-    }
-    fprintf(f, "\n");
+    print_summaries(f, nf, n, i, rows[i], sum.data(), mean.data(), top.data(), linked.data());  // (a cell has rows)
   }
   if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD grid output file!");
   if (pars.verbose >= 1)
@@ -656,7 +570,8 @@ void run_grid(ngsld_ctx *ctx, const Params &pars, GridArgs &ga, const ngsld_pos 
 
 // --cluster_out: one line per site of the input, in file order, its cluster or NA; --cluster_table: one line per cluster of
 // at least --cluster_min_size sites, in id order
-void run_clusters(ngsld_ctx *ctx, const Params &pars, ClusterArgs &ca, const ngsld_pos *pos) {
+void run_clusters(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  ClusterArgs &ca = cluster;
   ngsld_clusters_stats st{};
   st.struct_size = sizeof(st);
   if (ngsld_clusters(ctx, &ca.p, &st) != NGSLD_OK) error("ngsld_clusters", ngsld_last_error(ctx));
@@ -719,7 +634,8 @@ int write_blocks_text(void *user, const char *text, uint64_t len) {
   return fwrite(text, 1, len, static_cast<FILE *>(user)) == len ? 0 : 1;
 }
 
-void run_blocks(ngsld_ctx *ctx, const Params &pars, BlocksArgs &ba, const ngsld_pos *pos) {
+void run_blocks(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  BlocksArgs &ba = blocks;
   std::vector<const char *> lab(pars.n_sites);
   for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
   ngsld_blocks_stats st{};
@@ -756,7 +672,8 @@ void write_labels(const char *path, const std::vector<const char *> &labels) {
   if (fclose(f) != 0) error(__FUNCTION__, "cannot write pruning output file!");
 }
 
-void run_prune(ngsld_ctx *ctx, const Params &pars, PruneArgs &pa, const ngsld_pos *pos) {
+void run_prune(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  PruneArgs &pa = prune;
   std::vector<const char *> lab(pars.n_sites, "(null)");
   if (pos)
     for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
@@ -783,6 +700,95 @@ void run_prune(ngsld_ctx *ctx, const Params &pars, PruneArgs &pa, const ngsld_po
     fprintf(stderr, "==> Pruning: %lu nodes, %lu edges: %lu kept, %lu excluded (%lu rounds on the device, %lu nodes finished on the host)\n",
             (unsigned long)st.nodes, (unsigned long)st.edges, (unsigned long)st.kept, (unsigned long)st.excluded,
             (unsigned long)st.rounds, (unsigned long)st.host_nodes);
+}
+
+// ---- the analysis families, in the order they are taken out of argv, checked and run ----
+struct Family {
+  const char *prefix;  // of its flags, without the dashes; prefix + "out" names the family in the refusals
+  struct Valued {
+    const char *name;
+    const char **dst;
+  };
+  Valued valued[9];            // "--name value" or "--name=value"; a null name ends the list
+  const char *switch_name;     // a flag without a value (may be null) ...
+  bool *switch_on;             // ... and where it goes
+  bool *given;                 // any flag of the family
+  void (*check)(const Params &);  // once the reference's own arguments have been checked; only when given
+  void (*run)(ngsld_ctx *, const Params &, const ngsld_pos *);
+  const char *timing;          // its line of the NGSLD_TIMING report
+};
+const Family kFamilies[] = {
+    {"prune_",
+     {{"prune_out", &prune.out}, {"prune_excl", &prune.excl}, {"prune_subset", &prune.subset_file}, {"prune_field", &prune.field},
+      {"prune_weight_type", &prune.type}, {"prune_precision", &prune.precision}, {"prune_max_kb_dist", &prune.max_kb_dist},
+      {"prune_min_weight", &prune.min_weight}},
+     "prune_keep_heavy", &prune.keep_heavy, &prune.given, check_prune_args, run_prune, "pruning"},  // (a second pass of the pair kernels when the TSV was written too)
+    {"decay_",
+     {{"decay_out", &decay.out}, {"decay_fit", &decay.fit}, {"decay_ld", &decay.ld}, {"decay_bin_size", &decay.bin_size},
+      {"decay_max_kb_dist", &decay.max_kb_dist}, {"decay_min_maf", &decay.min_maf}, {"decay_n_ind", &decay.n_ind},
+      {"decay_recomb_rate", &decay.recomb_rate}},
+     nullptr, nullptr, &decay.given, check_decay_args, run_decay, "LD decay"},  // (a pass of the pair kernels of its own)
+    {"blocks_",
+     {{"blocks_out", &blocks.out}, {"blocks_chr", &blocks.chr}, {"blocks_start", &blocks.start}, {"blocks_end", &blocks.end},
+      {"blocks_ld", &blocks.ld}},
+     nullptr, nullptr, &blocks.given, check_blocks_args, run_blocks, "LD blocks"},  // (a pass of the pair kernels over the region's rows)
+    {"site_",
+     {{"site_out", &site.out}, {"site_ld", &site.ld}, {"site_max_kb_dist", &site.max_kb_dist}, {"site_min_maf", &site.min_maf},
+      {"site_linked_min", &site.linked_min}},
+     "site_signed", &site.is_signed, &site.given, check_site_args, run_site, "site LD"},  // (a pass of the pair kernels of its own)
+    {"cluster_",
+     {{"cluster_out", &cluster.out}, {"cluster_table", &cluster.table}, {"cluster_field", &cluster.field},
+      {"cluster_min_weight", &cluster.min_weight}, {"cluster_max_kb_dist", &cluster.max_kb_dist}, {"cluster_min_maf", &cluster.min_maf},
+      {"cluster_min_size", &cluster.min_size}},
+     "cluster_signed", &cluster.is_signed, &cluster.given, check_cluster_args, run_clusters, "LD clusters"},  // (a pass of its own)
+    {"grid_",
+     {{"grid_out", &grid.out}, {"grid_bin_size", &grid.bin_size}, {"grid_ld", &grid.ld}, {"grid_max_kb_dist", &grid.max_kb_dist},
+      {"grid_min_maf", &grid.min_maf}, {"grid_linked_min", &grid.linked_min}},
+     "grid_signed", &grid.is_signed, &grid.given, check_grid_args, run_grid, "LD grid"},  // (a pass of its own)
+};
+
+// Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
+void take_flags(int *argc, char **argv, const Family &fam) {
+  const size_t plen = std::strlen(fam.prefix);
+  int w = 1;
+  for (int i = 1; i < *argc; ++i) {
+    const char *a = argv[i];
+    if (std::strcmp(a, "--") == 0) {  // (getopt's end of options: the rest is not ours)
+      while (i < *argc) argv[w++] = argv[i++];
+      break;
+    }
+    const char *name = a[0] == '-' ? (a[1] == '-' ? a + 2 : a + 1) : nullptr;
+    if (name == nullptr || std::strncmp(name, fam.prefix, plen) != 0) {
+      argv[w++] = argv[i];
+      continue;
+    }
+    const char *eq = std::strchr(name, '=');
+    const std::string key = eq ? std::string(name, eq) : std::string(name);
+    *fam.given = true;
+    if (fam.switch_name != nullptr && key == fam.switch_name && eq == nullptr) {
+      *fam.switch_on = true;
+      continue;
+    }
+    bool known = false;
+    for (const Family::Valued *v = fam.valued; v->name != nullptr; ++v) {
+      if (key != v->name) continue;
+      known = true;
+      if (eq != nullptr) {
+        *v->dst = eq + 1;
+      } else if (i + 1 < *argc) {
+        *v->dst = argv[++i];
+      } else {
+        const std::string msg = "--" + key + " needs a value!";
+        error(__FUNCTION__, msg.c_str());
+      }
+    }
+    if (!known) {
+      const std::string msg = "unknown option --" + key + "!";
+      error(__FUNCTION__, msg.c_str());
+    }
+  }
+  argv[w] = nullptr;
+  *argc = w;
 }
 
 void parse_cmd_args(Params *pars, int argc, char **argv) {
@@ -1197,27 +1203,16 @@ int main(int argc, char **argv) {
   // mapping became fork-proof); this process is short-lived, single-purpose and never forks.  NGSLD_PIN_REGISTER=0 turns it off.
   setenv("NGSLD_PIN_REGISTER", "1", /*overwrite=*/0);
   Params pars;
-  PruneArgs prune;
-  take_prune_args(&argc, argv, &prune);
-  DecayArgs decay;
-  take_decay_args(&argc, argv, &decay);
-  BlocksArgs blocks;
-  take_blocks_args(&argc, argv, &blocks);
-  SiteArgs site;
-  take_site_args(&argc, argv, &site);
-  ClusterArgs cluster;
-  take_cluster_args(&argc, argv, &cluster);
-  GridArgs grid;
-  take_grid_args(&argc, argv, &grid);
+  for (const Family &fam : kFamilies) take_flags(&argc, argv, fam);
   parse_cmd_args(&pars, argc, argv);
-  check_prune_args(pars, &prune);
-  check_decay_args(pars, &decay);
-  check_blocks_args(pars, &blocks);
-  check_site_args(pars, &site);
-  check_cluster_args(pars, &cluster);
-  check_grid_args(pars, &grid);
+  bool any_family = false;
+  for (const Family &fam : kFamilies)
+    if (*fam.given) {
+      any_family = true;
+      fam.check(pars);
+    }
   // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out without --out: no TSV
-  const bool write_tsv = !(prune.given || decay.given || blocks.given || site.given || cluster.given || grid.given) || pars.out != NULL;
+  const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
   struct stat st;
@@ -1355,18 +1350,12 @@ int main(int argc, char **argv) {
     // From 4 GiB: a 1.2 GB file ran 0.5 s faster resident (2.2 s) than in slabs, a 5.8 GB one 0.5 s slower.
     slab_sites = std::min<uint64_t>(ngsld_sites_for_budget(pars.n_ind, budget, copies), (pars.n_sites + 5) / 6);
   }
-  if (slab_sites > 0 && prune.given)
-    error(__FUNCTION__, "--prune_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
-  if (slab_sites > 0 && decay.given)
-    error(__FUNCTION__, "--decay_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
-  if (slab_sites > 0 && blocks.given)
-    error(__FUNCTION__, "--blocks_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
-  if (slab_sites > 0 && site.given)
-    error(__FUNCTION__, "--site_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
-  if (slab_sites > 0 && cluster.given)
-    error(__FUNCTION__, "--cluster_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
-  if (slab_sites > 0 && grid.given)
-    error(__FUNCTION__, "--grid_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!");
+  for (const Family &fam : kFamilies)
+    if (slab_sites > 0 && *fam.given) {
+      const std::string msg = std::string("--") + fam.prefix +
+                              "out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be cut into slabs!";
+      error(__FUNCTION__, msg.c_str());
+    }
   if (slab_sites > 0) {
     join_early();  // (an early read is only started for matrices far below these thresholds: normally nothing to wait for)
     early.raw.reset();
@@ -1505,30 +1494,11 @@ int main(int argc, char **argv) {
   timing_report.mark("pair kernels + text + write");
   if (rc == NGSLD_ERR_MAF_RANGE) error("haplo_freq", ngsld_last_error(ctx));
   if (rc != NGSLD_OK) error("ngsld_run", ngsld_last_error(ctx));
-  if (prune.given) {  // (a second pass of the pair kernels when the TSV was written too)
-    run_prune(ctx, pars, prune, pos);
-    timing_report.mark("pruning");
-  }
-  if (decay.given) {  // (a pass of the pair kernels of its own)
-    run_decay(ctx, pars, decay);
-    timing_report.mark("LD decay");
-  }
-  if (blocks.given) {  // (a pass of the pair kernels over the region's rows)
-    run_blocks(ctx, pars, blocks, pos);
-    timing_report.mark("LD blocks");
-  }
-  if (site.given) {  // (a pass of the pair kernels of its own)
-    run_site(ctx, pars, site, pos);
-    timing_report.mark("site LD");
-  }
-  if (cluster.given) {  // (a pass of the pair kernels of its own)
-    run_clusters(ctx, pars, cluster, pos);
-    timing_report.mark("LD clusters");
-  }
-  if (grid.given) {  // (a pass of the pair kernels of its own)
-    run_grid(ctx, pars, grid, pos);
-    timing_report.mark("LD grid");
-  }
+  for (const Family &fam : kFamilies)
+    if (*fam.given) {
+      fam.run(ctx, pars, pos);
+      timing_report.mark(fam.timing);
+    }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share
                             // here means pairs computed at the host's speed: two nearly monomorphic sites each)
     ngsld_replay_stats_t st{};

@@ -2,9 +2,9 @@
 // ngsld_prune prunes, from the pair records where they are computed; no TSV and no edge list, one word per site.  CLUSTERS.md
 // has the rule, the deviations and why the result does not depend on the order of the atomics.
 //
-//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//   pairs    RecordPass (record_pass.h): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
 //            (replayed pairs carry their replayed values)
-//   union    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: both sites
+//   union    one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: both sites
 //            are marked as nodes, the edge filter on the printed value in integer micro-units (ld_prune.h), and every edge unites
 //            its two sites in parent[n_sites] -- a lock-free union-find that lives on the device across the chunks.  A root is
 //            only ever hooked under a smaller site, with a compare-and-swap on the root's own word: parent[v] <= v and only
@@ -17,7 +17,7 @@
 //            roots, sizes, last sites, edges and sums folded by root, one rounding for the mean and the density (ld_mean.h)
 #include "engine.h"
 #include "ld_prune.h"
-#include "ld_records.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -159,23 +159,15 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
   if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "clusters min_maf is NaN");
   if (std::isnan(p->min_weight)) return fail(c, NGSLD_ERR_INVALID, "clusters min_weight is NaN");
   const uint64_t n = c->n_sites;
-  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->clear_clusters();
   ngsld_clusters_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
+  if (const int rc = begin_pass(c, S)) return rc;
+  c->clear_clusters();
   hipStream_t st = c->stream;
 
   // ---- sites: the dist prefix sums (the limit and the spans come from them), the maf filter on the printed maf ----
-  std::vector<double> cum;
-  std::vector<uint32_t> infc;
-  if (!dist_prefix(c, cum, infc)) return fail(c, NGSLD_ERR_UNSUPPORTED, "clusters need integer position gaps");
-  std::vector<uint8_t> maf_ok(n);
-  for (uint64_t s = 0; s < n; ++s) {
-    const double m = c->h_maf[s];
-    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes)
-  }
+  SiteFilter F;
+  F.prepare(c, &p->min_maf);
+  if (!F.exact_gaps) return fail(c, NGSLD_ERR_UNSUPPORTED, "clusters need integer position gaps");
   const uint64_t chunk = record_chunk(test_knob("CLUSTER_CHUNK_PAIRS"));
   const uint64_t n_pairs = c->h_row_off[n];
   S.pairs = n_pairs;
@@ -188,35 +180,26 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
   // every partial sum of a cluster is exact while max |q| * its edges < 2^63: certain below 2^25 edges (|q| < 2^38)
   const bool track_max = n_pairs >= (1ull << 25);
   if (n_pairs > 0) {
-    DevBuf<double> d_cum;
-    DevBuf<uint32_t> d_infc, d_parent;
-    DevBuf<uint8_t> d_maf_ok, d_node;
+    DevBuf<uint32_t> d_parent;
+    DevBuf<uint8_t> d_node;
     DevBuf<unsigned long long> d_acc, d_meta;
-    HIP_TRY(c, d_cum.resize(n));
-    HIP_TRY(c, d_infc.resize(n));
+    if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_parent.resize(n));
-    HIP_TRY(c, d_maf_ok.resize(n));
     HIP_TRY(c, d_node.resize(n));
     HIP_TRY(c, d_acc.resize(2 * n));
     HIP_TRY(c, d_meta.resize(2));
-    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemsetAsync(d_node.p, 0, n, st));
     HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, 2 * n * sizeof(unsigned long long), st));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(init_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_parent.p, (uint32_t)n);
     HIP_TRY(c, hipGetLastError());
-    const uint64_t rec_cap = record_cap(c, chunk);
-    DevBuf<ngsld_rec_std> d_rec;
-    HIP_TRY(c, d_rec.resize(rec_cap));
-    EventPair ev;
-    HIP_TRY(c, ev.create());
+    RecordPass R;
+    if (const int rc = R.open(c, chunk)) return rc;
     ClusterArgs A{};
-    A.rec = d_rec.p;
-    A.cum = d_cum.p;
-    A.infc = d_infc.p;
-    A.maf_ok = d_maf_ok.p;
+    A.rec = R.records();
+    A.cum = F.d_cum.p;
+    A.infc = F.d_infc.p;
+    A.maf_ok = F.d_maf_ok.p;
     A.limit = p->max_kb_dist * 1000.0;
     A.min_weight = p->min_weight;
     A.field = p->field - 4;
@@ -228,25 +211,18 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
     A.acc = d_acc.p;
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
-    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
-      A.out_base = c->h_row_off[r0];
-      const int rcl = launch_record_items(c, ev, r0, r1, &S.union_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
-        A.items = items;
-        A.n_items = n_items;
-        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-        hipLaunchKernelGGL(union_kernel, dim3(blocks), dim3(256), 0, st, A);
-        ++S.union_launches;
-      });
-      if (rcl != NGSLD_OK) return rcl;
+    const int rc = R.run(&S.pairs_ms, &S.union_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+      A.out_base = ch.out_base;
+      A.items = items;
+      A.n_items = n_items;
+      const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+      hipLaunchKernelGGL(union_kernel, dim3(blocks), dim3(256), 0, st, A);
+      ++S.union_launches;
+    }, [&](const RecordChunk &) -> int {
       unsigned long long bad = 0;
       HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      if (bad != 0) {
-        const unsigned long long k = bad - 1;
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "a clusters value of the pair of sites " + std::to_string(k >> 32) + " - " +
-                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
-      }
-      return NGSLD_OK;
+      return bad != 0 ? fail_value_range(c, "clusters", bad) : NGSLD_OK;
     });
     if (rc != NGSLD_OK) return rc;
     const auto t_fin = std::chrono::steady_clock::now();
@@ -291,14 +267,14 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
   K.density.resize(nk);
   for (size_t k = 0; k < nk; ++k) {
     const uint64_t size = K.size[k], edges = K.edges[k];
-    if (track_max && edges >= (1ull << 25) && (unsigned __int128)meta[1] * edges >= ((unsigned __int128)1 << 63)) {
+    if (track_max && edges >= (1ull << 25) && sum_may_wrap(meta[1], edges)) {
       c->clear_clusters();
       return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(edges) + " edges with values too large to sum exactly");
     }
     S.edges += edges;
     if (size >= 2) ++S.clusters_multi;
     S.largest = std::max<uint64_t>(S.largest, size);
-    K.span[k] = (uint64_t)(cum[K.last[k]] - cum[K.first[k]]);
+    K.span[k] = (uint64_t)(F.cum[K.last[k]] - F.cum[K.first[k]]);
     const int64_t sum = K.sum[k];
     if (edges == 0) {
       K.mean[k] = std::numeric_limits<double>::quiet_NaN();

@@ -2,9 +2,9 @@
 // records where they are computed -- no TSV; a few hundred bin means leave the device.  DECAY.md has the rule, the deviations
 // and why the sums are exact.
 //
-//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//   pairs    RecordPass (record_pass.h): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
 //            (replayed pairs carry their replayed values)
-//   bins     one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the filters,
+//   bins     one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: the filters,
 //            dist as the TSV prints it (dist_prefix), the right-closed bin, each chosen field as its printed value in integer
 //            micro-units (ld_prune.h).  dist rises with the candidate, so a wavefront's lanes fall in a few runs of one bin: a
 //            segmented scan merges each run and its last lane adds once, into a per-workgroup LDS histogram flushed once per
@@ -13,7 +13,7 @@
 //            bin's mean is the double nearest to sum / (10^6 * rows)
 #include "engine.h"
 #include "ld_prune.h"
-#include "ld_records.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -169,15 +169,12 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "decay max_kb_dist must be >= 0");
   if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "decay min_maf is NaN");
   const uint64_t n = c->n_sites;
-  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
+  ngsld_decay_stats S;
+  if (const int rc = begin_pass(c, S)) return rc;
   c->decay_fields = 0;
   c->decay_dist.clear();
   c->decay_mean.clear();
   c->decay_count.clear();
-  ngsld_decay_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
   hipStream_t st = c->stream;
   int field[4] = {0, 0, 0, 0};
   const int ns = field_list(p->fields, field);
@@ -185,16 +182,11 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
 
   // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
   const double limit = p->max_kb_dist * 1000.0;
-  std::vector<double> cum;
-  std::vector<uint32_t> infc;
-  const bool exact_gaps = dist_prefix(c, cum, infc);  // integer gaps >= 0
-  std::vector<uint8_t> maf_ok(n);
-  for (uint64_t s = 0; s < n; ++s) {
-    const double m = c->h_maf[s];
-    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes, as in R)
-  }
-  if (!exact_gaps && std::isfinite(limit))
-    return fail(c, NGSLD_ERR_UNSUPPORTED, "decay max_kb_dist needs integer position gaps");
+  SiteFilter F;
+  F.prepare(c, &p->min_maf);
+  if (const int rc = F.check_limit(c, "decay", limit)) return rc;
+  const std::vector<double> &cum = F.cum;
+  const std::vector<uint32_t> &infc = F.infc;
 
   // ---- bins sized from the plan: the largest finite planned dist, capped by the limit ----
   uint64_t n_slots = 0;
@@ -212,7 +204,7 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
       const uint64_t s2 = std::min<uint64_t>(c->h_row_end[s1] - 1, chr_last[infc[s1]]);
       if (s2 <= s1) continue;
       // gaps >= 0 (every position file): dist rises along the row; any other gaps: the chromosome's span bounds it
-      const double d = exact_gaps ? cum[s2] - cum[s1] : chr_hi[infc[s1]] - chr_lo[infc[s1]];
+      const double d = F.exact_gaps ? cum[s2] - cum[s1] : chr_hi[infc[s1]] - chr_lo[infc[s1]];
       dmax = std::max(dmax, printed_dist(d));
     }
     if (dmax >= limit) dmax = limit;  // (dist < limit: the limit's own bin is the last one that can fill)
@@ -236,29 +228,18 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
   std::vector<unsigned __int128> sum(ns * n_slots, 0);
   std::vector<uint64_t> count(n_slots, 0);
   if (n_slots > 0 && n_pairs > 0) {
-    DevBuf<double> d_cum;
-    DevBuf<uint32_t> d_infc;
-    DevBuf<uint8_t> d_maf_ok;
     DevBuf<unsigned long long> d_acc, d_meta;
-    HIP_TRY(c, d_cum.resize(n));
-    HIP_TRY(c, d_infc.resize(n));
-    HIP_TRY(c, d_maf_ok.resize(n));
+    if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_acc.resize(W));
     HIP_TRY(c, d_meta.resize(3));
-    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    const uint64_t rec_cap = record_cap(c, chunk);
-    DevBuf<ngsld_rec_std> d_rec;
-    HIP_TRY(c, d_rec.resize(rec_cap));
-    EventPair ev;
-    HIP_TRY(c, ev.create());
+    RecordPass R;
+    if (const int rc = R.open(c, chunk)) return rc;
     BinArgs A{};
-    A.rec = d_rec.p;
-    A.cum = d_cum.p;
-    A.infc = d_infc.p;
-    A.maf_ok = d_maf_ok.p;
+    A.rec = R.records();
+    A.cum = F.d_cum.p;
+    A.infc = F.d_infc.p;
+    A.maf_ok = F.d_maf_ok.p;
     A.limit = limit;
     A.bin = B;
     A.n_slots = (uint32_t)n_slots;
@@ -268,33 +249,29 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
     A.meta = d_meta.p;
     std::vector<unsigned long long> h_acc(W);
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t np) -> int {
-      A.out_base = c->h_row_off[r0];
-      A.track_max = np > kRecordChunkPairs ? 1 : 0;
+    const int rc = R.run(&S.pairs_ms, &S.bin_ms, &S.chunks, [&](const RecordChunk &ch) -> int {
+      A.track_max = ch.pairs > kRecordChunkPairs ? 1 : 0;
       HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
-      const int rcl = launch_record_items(c, ev, r0, r1, &S.bin_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
-        A.items = items;
-        A.n_items = n_items;
-        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-        if (use_lds)
-          hipLaunchKernelGGL(bin_kernel<true>, dim3(blocks), dim3(256), (size_t)W * 8, st, A);
-        else
-          hipLaunchKernelGGL(bin_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-      });
-      if (rcl != NGSLD_OK) return rcl;
+      return NGSLD_OK;
+    }, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+      A.out_base = ch.out_base;
+      A.items = items;
+      A.n_items = n_items;
+      const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+      if (use_lds)
+        hipLaunchKernelGGL(bin_kernel<true>, dim3(blocks), dim3(256), (size_t)W * 8, st, A);
+      else
+        hipLaunchKernelGGL(bin_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+    }, [&](const RecordChunk &ch) -> int {
       unsigned long long meta[3] = {0, 0, 0};
       HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      if (meta[0] != 0) {
-        const unsigned long long k = meta[0] - 1;
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "a decay value of the pair of sites " + std::to_string(k >> 32) + " - " +
-                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
-      }
+      if (meta[0] != 0) return fail_value_range(c, "decay", meta[0]);
       if (meta[2] != 0) return fail(c, NGSLD_ERR_INVALID, "decay: a row fell beyond the planned bins (internal error)");
       // a row longer than a chunk is one chunk: every partial sum of it is exact when max |q| * pairs < 2^63
-      if (A.track_max && meta[1] > 0 && (unsigned __int128)meta[1] * np >= ((unsigned __int128)1 << 63))
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(np) + " pairs with values too large to sum exactly");
+      if (A.track_max && sum_may_wrap(meta[1], ch.pairs))
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(ch.pairs) + " pairs with values too large to sum exactly");
       for (uint64_t k = 0; k < n_slots; ++k) {
         count[k] += h_acc[k];
         for (int v = 0; v < ns; ++v) sum[v * n_slots + k] += (unsigned __int128)(__int128)(int64_t)h_acc[(1 + v) * n_slots + k];

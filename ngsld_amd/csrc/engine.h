@@ -586,56 +586,7 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
 // host writer adds the gaps one by one.
 bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc);
 
-// ---- record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks (blocks.hip), ngsld_site_ld (site_ld.hip),
-// ngsld_clusters (cluster.hip) and ngsld_grid (grid.hip) read the records of
-// rows chunk by chunk and run a kernel of their own over each chunk's items (ld_records.h) ----
-// records of one chunk of rows (32 B each)
-constexpr uint64_t kRecordChunkPairs = 1ull << 24;
-// the chunk of a pass: kRecordChunkPairs, or a test knob's smaller value (knob: test_knob("NAME") or null)
-inline uint64_t record_chunk(const char *knob) {
-  return knob ? std::max<uint64_t>(1, std::min<uint64_t>(kRecordChunkPairs, std::strtoull(knob, nullptr, 10))) : kRecordChunkPairs;
-}
-// The rows a pass runs: every row, or the rows s with rows[s] != 0.
-// records a pass with chunks of `chunk` needs: the chunk (at most the rows' pairs), or the longest row when one is longer (a
-// row is never cut)
-uint64_t record_cap(const ngsld_ctx *c, uint64_t chunk, const uint8_t *rows = nullptr);
-
-// The rows chunk by chunk into d_rec (room for rec_cap records): chunks of consecutive rows, up to chunk_pairs records, a
-// longer row is a chunk of its own (NGSLD_ERR_UNSUPPORTED past rec_cap): ngsld_run_device + ngsld_finish_device on the
-// context's stream, so every record is final (replayed pairs carry their replayed values), then on_chunk(r0, r1, pairs) for
-// the chunk's rows [r0, r1).  *pairs_ms adds the wall time of the pair phase.  ngsld_prune and ngsld_decay read the records
-// of every row this way, ngsld_blocks those of the region's rows.
-int run_record_chunks(ngsld_ctx *c, uint64_t chunk_pairs, ngsld_rec_std *d_rec, uint64_t rec_cap, double *pairs_ms,
-                      const std::function<int(uint64_t r0, uint64_t r1, uint64_t pairs)> &on_chunk, const uint8_t *rows = nullptr);
-
-// two events that bracket device work on the context's stream; add_elapsed: *ms += their span once the second has passed
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  EventPair() = default;
-  EventPair(const EventPair &) = delete;
-  EventPair &operator=(const EventPair &) = delete;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  hipError_t create() {
-    hipError_t e = hipEventCreate(&a);
-    return e == hipSuccess ? hipEventCreate(&b) : e;
-  }
-  hipError_t add_elapsed(double *ms) const {
-    float t = 0.f;
-    const hipError_t e = hipEventElapsedTime(&t, a, b);
-    if (e == hipSuccess) *ms += t;
-    return e;
-  }
-};
-
-// A chunk's launches (inside run_record_chunks' on_chunk): launch(items, n_items) for each slice of the items of rows [r0, r1),
-// every slice below 2^32 threads at one wavefront per item, all of them between ev's two events on the context's stream; then
-// waits for the second, adds the span to *ms and counts the chunk in *chunks (when not null)
-int launch_record_items(ngsld_ctx *c, EventPair &ev, uint64_t r0, uint64_t r1, double *ms, uint64_t *chunks,
-                        const std::function<void(const ngsld_item *items, uint64_t n_items)> &launch);
-
+// ---- record passes: their host frame is record_pass.h ----
 // what the entries of the record passes share
 inline unsigned blocks_for(uint64_t threads, unsigned per_block = 256) { return (unsigned)((threads + per_block - 1) / per_block); }
 inline double ms_since(std::chrono::steady_clock::time_point t0) {

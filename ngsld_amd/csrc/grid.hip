@@ -6,9 +6,9 @@
 //   bins     host: each label's CHR:pos (up to the first TAB), bin(s) = pos / B; gbin[s] numbers the bins consecutively over the
 //            chromosomes; the band K is the furthest a row's bins reach (from the plan's row_end); cell (s1, s2) is word
 //            gbin[s1] * K + (gbin[s2] - gbin[s1]) of each of the 1 + 3 * fields accumulators
-//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//   pairs    RecordPass (record_pass.h): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
 //            (replayed pairs carry their replayed values)
-//   cells    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the filters,
+//   cells    one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: the filters,
 //            each chosen field as its printed value in integer micro-units (ld_prune.h).  The lanes of an item share s1 and
 //            their gbin[s2] never decreases: they fall into a few runs of one cell.  One ballot numbers the runs, a segmented
 //            scan merges each (counts, sums, maxima: six steps), and the run's last lane adds once per word -- never an atomic
@@ -22,7 +22,7 @@
 
 #include "engine.h"
 #include "ld_prune.h"
-#include "ld_records.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -33,8 +33,6 @@ namespace {
 constexpr uint32_t kLdsMax = 64u << 10, kLdsDefault = 4u << 10;
 // rows of a tile
 constexpr uint32_t kTileRows = 16;
-// a maximum is kept as q + kMaxBias > 0 (|q| < 2^38): 0 is "no row yet", and an unsigned max does the rest
-constexpr unsigned long long kMaxBias = 1ull << 38;
 // the accumulators of a call: (1 + 3 * fields) x cells x 8 B
 constexpr uint64_t kMaxAccBytes = 2ull << 30;
 
@@ -63,8 +61,6 @@ struct GridArgs {
   unsigned long long *acc;    // [1 + 3 * ns][cells]: rows; then per field the int64 sum (two's complement), the biased maximum, the linked rows
   unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|, [2] a cell beyond the band
 };
-
-__device__ __forceinline__ bool is_max_word(uint32_t w) { return w > 0 && (w - 1) % 3 == 1; }
 
 // word w of cell (row bin, offset k): in the tile's LDS window where the row bin lies in it, else in global memory
 template <bool kLds>
@@ -213,12 +209,6 @@ __global__ __launch_bounds__(256) void grid_kernel(GridArgs A) {
   }
 }
 
-// the label's part up to its first TAB (a pos file with extra columns puts them behind one)
-std::string label_key(const char *l) {
-  const char *t = std::strchr(l, '\t');
-  return t ? std::string(l, t) : std::string(l);
-}
-
 }  // namespace
 
 extern "C" {
@@ -235,12 +225,9 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
   if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "grid linked_min is NaN");
   if (labels == nullptr) return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: the labels are NULL");
   const uint64_t n = c->n_sites;
-  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->clear_grid();
   ngsld_grid_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
+  if (const int rc = begin_pass(c, S)) return rc;
+  c->clear_grid();
   hipStream_t st = c->stream;
   int field[4] = {0, 0, 0, 0};
   const int ns = field_list(p->fields, field);
@@ -249,16 +236,9 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
 
   // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
   const double limit = p->max_kb_dist * 1000.0;
-  std::vector<double> cum;
-  std::vector<uint32_t> infc;
-  const bool exact_gaps = dist_prefix(c, cum, infc);  // integer gaps >= 0
-  if (!exact_gaps && std::isfinite(limit))
-    return fail(c, NGSLD_ERR_UNSUPPORTED, "grid max_kb_dist needs integer position gaps");
-  std::vector<uint8_t> maf_ok(n);
-  for (uint64_t s = 0; s < n; ++s) {
-    const double m = c->h_maf[s];
-    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes)
-  }
+  SiteFilter F;
+  F.prepare(c, &p->min_maf);
+  if (const int rc = F.check_limit(c, "grid", limit)) return rc;
 
   // ---- bins: each label's CHR:pos; a chromosome is a run of sites between the +inf gaps of pos_dist ----
   struct Chr {
@@ -274,16 +254,12 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
     uint64_t prev_pos = 0;
     for (uint64_t s = 0; s < n; ++s) {
       if (labels[s] == nullptr) return fail(c, NGSLD_ERR_INVALID, "a label is NULL");
-      const std::string key = label_key(labels[s]);
+      const LabelPos L = label_pos(labels[s]);
+      const std::string &key = L.key, name = L.chr();
       if (key == "(null)") return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: a label is \"(null)\"");
-      const size_t colon = key.find(':');
-      const std::string name = key.substr(0, colon);
-      const std::string num = colon == std::string::npos ? std::string() : key.substr(colon + 1);
-      bool digits = !num.empty() && num.size() <= 19;
-      for (char ch : num) digits = digits && ch >= '0' && ch <= '9';
-      if (!digits) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of label \"" + key + "\" is not plain decimal digits");
-      const uint64_t pos = std::strtoull(num.c_str(), nullptr, 10);
-      const bool new_run = s == 0 || infc[s] != infc[s - 1];
+      uint64_t pos = 0;
+      if (!L.position(&pos)) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of label \"" + key + "\" is not plain decimal digits");
+      const bool new_run = s == 0 || F.infc[s] != F.infc[s - 1];
       if (new_run) {
         if (s > 0 && name == chrs.back().name)
           return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: site \"" + key + "\" is on the chromosome of the site before it, \"" + prev_key +
@@ -366,34 +342,24 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
   const size_t W = (size_t)words * cells;
   std::vector<unsigned long long> h_acc(W, 0);
   if (n_pairs > 0 && cells > 0) {
-    DevBuf<double> d_cum;
-    DevBuf<uint32_t> d_infc, d_gbin;
-    DevBuf<uint8_t> d_maf_ok;
+    DevBuf<uint32_t> d_gbin;
     DevBuf<unsigned long long> d_acc, d_meta;
-    HIP_TRY(c, d_cum.resize(n));
-    HIP_TRY(c, d_infc.resize(n));
+    if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_gbin.resize(n));
-    HIP_TRY(c, d_maf_ok.resize(n));
     HIP_TRY(c, d_acc.resize(W));
     HIP_TRY(c, d_meta.resize(3));
-    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_gbin.p, gbin.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    const uint64_t rec_cap = record_cap(c, chunk);
-    DevBuf<ngsld_rec_std> d_rec;
-    HIP_TRY(c, d_rec.resize(rec_cap));
-    EventPair ev;
-    HIP_TRY(c, ev.create());
+    RecordPass R;
+    if (const int rc = R.open(c, chunk)) return rc;
     GridArgs A{};
     A.items = c->d_items.p;
     A.item_off = c->d_item_off.p;
-    A.rec = d_rec.p;
-    A.cum = d_cum.p;
-    A.infc = d_infc.p;
-    A.maf_ok = d_maf_ok.p;
+    A.rec = R.records();
+    A.cum = F.d_cum.p;
+    A.infc = F.d_infc.p;
+    A.maf_ok = F.d_maf_ok.p;
     A.gbin = d_gbin.p;
     A.limit = limit;
     A.linked_min = p->linked_min;
@@ -411,30 +377,24 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
     const size_t lds_bytes = use_lds ? (size_t)words * tile_bins * band * 8 : 0;
-    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
-      A.out_base = c->h_row_off[r0];
-      A.r0 = r0;
-      A.r1 = r1;
-      const int rcl = launch_record_items(c, ev, r0, r1, &S.grid_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
-        A.i0 = (uint64_t)(items - c->d_items.p);
-        A.i1 = A.i0 + n_items;
-        if (use_lds) {
-          const unsigned tiles = blocks_for(r1 - r0, A.tile_rows);
-          hipLaunchKernelGGL(grid_kernel<true>, dim3(tiles), dim3(256), lds_bytes, st, A);
-        } else {
-          const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-          hipLaunchKernelGGL(grid_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-        }
-      });
-      if (rcl != NGSLD_OK) return rcl;
+    const int rc = R.run(&S.pairs_ms, &S.grid_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+      A.out_base = ch.out_base;
+      A.r0 = ch.r0;
+      A.r1 = ch.r1;
+      A.i0 = (uint64_t)(items - c->d_items.p);
+      A.i1 = A.i0 + n_items;
+      if (use_lds) {
+        const unsigned tiles = blocks_for(ch.r1 - ch.r0, A.tile_rows);
+        hipLaunchKernelGGL(grid_kernel<true>, dim3(tiles), dim3(256), lds_bytes, st, A);
+      } else {
+        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+        hipLaunchKernelGGL(grid_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+      }
+    }, [&](const RecordChunk &) -> int {
       unsigned long long meta[3] = {0, 0, 0};
       HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      if (meta[0] != 0) {
-        const unsigned long long k = meta[0] - 1;
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "a grid value of the pair of sites " + std::to_string(k >> 32) + " - " +
-                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
-      }
+      if (meta[0] != 0) return fail_value_range(c, "grid", meta[0]);
       if (meta[2] != 0) return fail(c, NGSLD_ERR_INVALID, "LD grid: a pair beyond the band of its row (internal error)");
       return NGSLD_OK;
     });
@@ -443,7 +403,7 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
     HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    if (A.track_max && meta[1] > 0 && (unsigned __int128)meta[1] * cell_rows >= ((unsigned __int128)1 << 63))
+    if (A.track_max && sum_may_wrap(meta[1], cell_rows))
       return fail(c, NGSLD_ERR_UNSUPPORTED, "a grid cell of up to " + std::to_string(cell_rows) + " pairs with values too large to sum exactly");
   }
 
@@ -475,17 +435,14 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
   G.linked.resize((size_t)ns * n_cells);
   G.mean.resize((size_t)ns * n_cells);
   for (int v = 0; v < ns; ++v) {
-    const unsigned long long *a_sum = h_acc.data() + (size_t)(1 + 3 * v) * cells, *a_max = a_sum + cells, *a_linked = a_max + cells;
     size_t k = (size_t)v * n_cells;
     for (uint64_t w = 0; w < cells; ++w) {
-      const uint64_t rows = h_acc[w];
-      if (rows == 0) continue;
-      const int64_t sum = (int64_t)a_sum[w];
-      G.sum[k] = sum;
-      G.max[k] = (int64_t)(a_max[w] - kMaxBias);
-      G.linked[k] = a_linked[w];
-      const double m = mean_nearest(sum < 0 ? (uint64_t)0 - (uint64_t)sum : (uint64_t)sum, rows);
-      G.mean[k] = sum < 0 ? -m : m;
+      if (h_acc[w] == 0) continue;
+      const FieldSummary f = field_summary(h_acc.data(), cells, v, w);
+      G.sum[k] = f.sum;
+      G.max[k] = f.max;
+      G.linked[k] = f.linked;
+      G.mean[k] = f.mean;
       ++k;
     }
   }

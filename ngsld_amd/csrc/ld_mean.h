@@ -34,7 +34,7 @@ inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
 }
 
 // the double nearest to sum / (10^6 * rows): the mean of `rows` printed values whose micro-units add up to `sum` (ngsld_grid's
-// cells, grid.hip: up to a million of them a field).  Where sum < 2^53 and rows < 2^33 both operands are doubles, and one IEEE
+// cells, up to a million of them a field, and ngsld_site_ld's sites: field_summary, record_pass.h).  Where sum < 2^53 and rows < 2^33 both operands are doubles, and one IEEE
 // division is that one rounding: the operands are exact, and a quotient of two integers below 2^53 never lies on a tie between
 // two doubles (a tie has 54 significant bits, hence a numerator of at least 2^53).  Elsewhere the long division.
 // tests/test_mean_nearest.py holds both branches to the exact quotient; GRID.md has what the short one saves.

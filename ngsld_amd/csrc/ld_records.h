@@ -1,5 +1,5 @@
 // ld_records.h -- the consumer side of the pair records on the device: which record a lane of a work item reads, a TSV
-// column's field of a record, a wavefront's max and sum.  Shared by the TSV rows (ld_text.hip) and the record passes of ngsld_prune,
+// column's field of a record, a wavefront's max and sum, the words of the sum / max / linked accumulators.  Shared by the TSV rows (ld_text.hip) and the record passes of ngsld_prune,
 // ngsld_decay, ngsld_blocks, ngsld_site_ld, ngsld_clusters and ngsld_grid (prune.hip, decay.hip, blocks.hip, site_ld.hip, cluster.hip,
 // grid.hip), which all map one wavefront to an item and one lane to a candidate.  Not part of the ld_device.h umbrella: the pair kernels never see it.
 #pragma once
@@ -21,6 +21,12 @@ __device__ __forceinline__ uint64_t record_of(const ngsld_item &it, uint32_t c, 
 __device__ __forceinline__ double field_of(const ngsld_rec_std &r, int f) {
   return f == 0 ? r.r2_ExpG : f == 1 ? r.D : f == 2 ? r.Dp : r.r2;
 }
+
+// The accumulators of ngsld_site_ld and ngsld_grid are words [1 + 3 * fields][entries]: rows; then per field the int64 sum (two's
+// complement), the maximum, the linked rows (record_pass.h unpacks them on the host).
+// a maximum is kept as q + kMaxBias > 0 (|q| < 2^38): 0 is "no row yet", and an unsigned max does the rest
+constexpr unsigned long long kMaxBias = 1ull << 38;
+__device__ __forceinline__ bool is_max_word(uint32_t w) { return w > 0 && (w - 1) % 3 == 1; }
 
 // the max of v over the 64 lanes, in every lane
 __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {

@@ -2,9 +2,9 @@
 // records where they are computed -- no TSV, and the graph leaves the device only as a small remainder.  PRUNE.md has the rule,
 // the deviations and why the parallel rounds end in the sequential rule's sets.
 //
-//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into
+//   pairs    RecordPass (record_pass.h): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into
 //            records (replayed pairs carry their replayed values)
-//   edges    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: node
+//   edges    one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: node
 //            marks, the printed-value filter (ld_prune.h), the surviving (s1, s2, label) compacted with one ballot and one
 //            atomic per wavefront
 //   graph    both directions of every edge radix-sorted by their first end (hipCUB): CSR offsets, neighbours, int64 weights
@@ -16,7 +16,7 @@
 
 #include "engine.h"
 #include "ld_prune.h"
-#include "ld_records.h"
+#include "record_pass.h"
 #include "../../include/ngsld_host.h"
 
 namespace {
@@ -256,11 +256,8 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   if (std::isnan(p->min_weight)) return fail(c, NGSLD_ERR_INVALID, "prune min_weight is NaN");
   if (p->n_subset > 0 && p->subset == nullptr) return fail(c, NGSLD_ERR_INVALID, "prune subset is NULL");
   const uint64_t n = c->n_sites;
-  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
   ngsld_prune_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
+  if (const int rc = begin_pass(c, S)) return rc;
   hipStream_t st = c->stream;
 
   // ---- sites: labels, ranks (lc(label), label, index), the subset, the dist prefix sums ----
@@ -287,22 +284,17 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     for (uint64_t s = 0; s < n; ++s) in_subset[s] = want.count(lab[s]) ? 1 : 0;
   }
   const double max_dist = p->max_kb_dist * 1000.0;
-  std::vector<double> cum;
-  std::vector<uint32_t> infc;
-  if (!dist_prefix(c, cum, infc) && std::isfinite(max_dist))
-    return fail(c, NGSLD_ERR_UNSUPPORTED, "prune max_kb_dist needs integer position gaps");
-  DevBuf<double> d_cum;
-  DevBuf<uint32_t> d_infc, d_rank;
+  SiteFilter F;
+  F.prepare(c, nullptr);
+  if (const int rc = F.check_limit(c, "prune", max_dist)) return rc;
+  DevBuf<uint32_t> d_rank;
   DevBuf<uint8_t> d_subset, d_node, d_mark;
   DevBuf<unsigned long long> d_meta;
-  HIP_TRY(c, d_cum.resize(n));
-  HIP_TRY(c, d_infc.resize(n));
+  if (const int rc = F.upload(c)) return rc;
   HIP_TRY(c, d_rank.resize(n));
   HIP_TRY(c, d_node.resize(n));
   HIP_TRY(c, d_mark.resize(n));
   HIP_TRY(c, d_meta.resize(4));
-  HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(d_rank.p, rank.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
   if (!in_subset.empty()) {
     HIP_TRY(c, d_subset.resize(n));
@@ -315,17 +307,14 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   // ---- pairs and edges, chunk of rows by chunk ----
   const uint64_t n_pairs = c->h_row_off[n];
   S.pairs = n_pairs;
-  DevBuf<ngsld_rec_std> d_rec;
   DevBuf<uint32_t> d_ea, d_eb;
   DevBuf<int64_t> d_el;
-  const uint64_t chunk_pairs = std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, kRecordChunkPairs));  // (a longer row is refused)
-  HIP_TRY(c, d_rec.resize(chunk_pairs));
-  EventPair ev;
-  HIP_TRY(c, ev.create());
+  RecordPass R;  // (a row longer than the chunk is refused)
+  if (const int rc = R.open(c, std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, kRecordChunkPairs)), nullptr, false)) return rc;
   EdgeArgs A{};
   A.field = p->field - 4;
-  A.cum = d_cum.p;
-  A.infc = d_infc.p;
+  A.cum = F.d_cum.p;
+  A.infc = F.d_infc.p;
   A.max_dist = max_dist;
   A.min_weight = p->min_weight;
   A.scale = prune_scale(p->precision);
@@ -333,11 +322,11 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   A.in_subset = in_subset.empty() ? nullptr : d_subset.p;
   A.node = d_node.p;
   A.meta = d_meta.p;
-  A.rec = d_rec.p;
+  A.rec = R.records();
   unsigned long long meta[4] = {0, 0, 0, 0};
-  const int rc_chunks = run_record_chunks(c, chunk_pairs, d_rec.p, chunk_pairs, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t np) -> int {
+  const int rc_chunks = R.run(&S.pairs_ms, &S.edges_ms, nullptr, [&](const RecordChunk &ch) -> int {
     // room for every pair of this chunk to be an edge
-    const uint64_t need = meta[0] + np;
+    const uint64_t need = meta[0] + ch.pairs;
     if (d_el.n < need) {
       const size_t cap = (size_t)std::max<uint64_t>(need, std::min<uint64_t>(n_pairs, 2 * (uint64_t)d_el.n));
       HIP_TRY(c, grow(d_ea, cap, meta[0], st));
@@ -348,13 +337,13 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     A.eb = d_eb.p;
     A.el = d_el.p;
     A.cap = d_el.n;
-    A.out_base = c->h_row_off[r0];
-    const int rc = launch_record_items(c, ev, r0, r1, &S.edges_ms, nullptr, [&](const ngsld_item *items, uint64_t n_items) {
-      A.items = items;
-      A.n_items = n_items;
-      hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(n_items * 64)), dim3(256), 0, st, A);
-    });
-    if (rc != NGSLD_OK) return rc;
+    A.out_base = ch.out_base;
+    return NGSLD_OK;
+  }, [&](const RecordChunk &, const ngsld_item *items, uint64_t n_items) {
+    A.items = items;
+    A.n_items = n_items;
+    hipLaunchKernelGGL(edge_kernel, dim3(blocks_for(n_items * 64)), dim3(256), 0, st, A);
+  }, [&](const RecordChunk &) -> int {
     HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (meta[3] != 0) {
@@ -365,7 +354,7 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
     return NGSLD_OK;
   });
   if (rc_chunks != NGSLD_OK) return rc_chunks;
-  d_rec.release();
+  R.close();
   const uint64_t E = meta[0];
   S.edges = E;
 

@@ -2,9 +2,9 @@
 // sum (the LD score), mean, maximum and linked partners of every site -- from the pair records where they are computed; no
 // TSV, a few numbers per site leave the device.  SITES.md has the rule, the deviations and why the sums are exact.
 //
-//   pairs    run_record_chunks (engine_run.hip): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
+//   pairs    RecordPass (record_pass.h): ngsld_run_device + ngsld_finish_device, chunk of rows by chunk, into records
 //            (replayed pairs carry their replayed values)
-//   sites    one wavefront per work item, one lane per candidate (ld_records.h), launched by launch_record_items: the filters,
+//   sites    one wavefront per work item, one lane per candidate (ld_records.h), launched once per slice of a chunk's items: the filters,
 //            each chosen field as its printed value in integer micro-units (ld_prune.h), added to BOTH sites of the pair.
 //            The row end: the 64 lanes of an item share s1 -- rows, sums, maximum and linked rows are reduced across the
 //            wavefront and added once per item.  The column end: the lanes of an item are 64 consecutive sites, and in a
@@ -14,10 +14,10 @@
 //            (all pairs, no window) every add is a global atomic.  Integer adds and maxima commute: every launch shape and
 //            order gives the same bits.
 //   host     the accumulators come back once, after the last chunk; a site's mean is the double nearest to
-//            sum / (10^6 * rows) (div_nearest, ld_mean.h)
+//            sum / (10^6 * rows) (mean_nearest, ld_mean.h)
 #include "engine.h"
 #include "ld_prune.h"
-#include "ld_records.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -25,8 +25,6 @@ namespace {
 // four workgroups (16 wavefronts) a compute unit; SITES.md has the measurements
 constexpr uint32_t kLdsBudget = 64u << 10;
 constexpr uint32_t kTileRows = 16;
-// a maximum is kept as q + kMaxBias > 0 (|q| < 2^38): 0 is "no row yet", and an unsigned max does the rest
-constexpr unsigned long long kMaxBias = 1ull << 38;
 
 struct SiteArgs {
   const ngsld_item *items;    // the context's items, all of them
@@ -49,8 +47,6 @@ struct SiteArgs {
   unsigned long long *acc;    // [1 + 3 * ns][n_sites]: rows; then per field the int64 sum (two's complement), the biased maximum, the linked rows
   unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|
 };
-
-__device__ __forceinline__ bool is_max_word(uint32_t w) { return w > 0 && (w - 1) % 3 == 1; }
 
 // word w of a site's accumulators: in the tile's LDS window where the site lies in it, else in global memory
 template <bool kLds>
@@ -183,12 +179,9 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
   if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "site_ld min_maf is NaN");
   if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "site_ld linked_min is NaN");
   const uint64_t n = c->n_sites;
-  if (n >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "n_sites must be below 2^32 - 1");
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->clear_sites();
   ngsld_site_ld_stats S;
-  std::memset(&S, 0, sizeof(S));
-  S.struct_size = sizeof(S);
+  if (const int rc = begin_pass(c, S)) return rc;
+  c->clear_sites();
   hipStream_t st = c->stream;
   int field[4] = {0, 0, 0, 0};
   const int ns = field_list(p->fields, field);
@@ -196,16 +189,9 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
 
   // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
   const double limit = p->max_kb_dist * 1000.0;
-  std::vector<double> cum;
-  std::vector<uint32_t> infc;
-  const bool exact_gaps = dist_prefix(c, cum, infc);  // integer gaps >= 0
-  if (!exact_gaps && std::isfinite(limit))
-    return fail(c, NGSLD_ERR_UNSUPPORTED, "site_ld max_kb_dist needs integer position gaps");
-  std::vector<uint8_t> maf_ok(n);
-  for (uint64_t s = 0; s < n; ++s) {
-    const double m = c->h_maf[s];
-    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= p->min_maf) ? 1 : 0;  // (a NaN maf never passes)
-  }
+  SiteFilter F;
+  F.prepare(c, &p->min_maf);
+  if (const int rc = F.check_limit(c, "site_ld", limit)) return rc;
 
   // ---- from the plan: how far a row reaches (the LDS window of a tile), how many rows a site can be in (the sums' bound) ----
   uint64_t span = 0, degree_max = 0;
@@ -235,32 +221,21 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
   const size_t W = (size_t)words * n;
   std::vector<unsigned long long> h_acc(W, 0);
   if (n_pairs > 0) {
-    DevBuf<double> d_cum;
-    DevBuf<uint32_t> d_infc;
-    DevBuf<uint8_t> d_maf_ok;
     DevBuf<unsigned long long> d_acc, d_meta;
-    HIP_TRY(c, d_cum.resize(n));
-    HIP_TRY(c, d_infc.resize(n));
-    HIP_TRY(c, d_maf_ok.resize(n));
+    if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_acc.resize(W));
     HIP_TRY(c, d_meta.resize(2));
-    HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
-    const uint64_t rec_cap = record_cap(c, chunk);
-    DevBuf<ngsld_rec_std> d_rec;
-    HIP_TRY(c, d_rec.resize(rec_cap));
-    EventPair ev;
-    HIP_TRY(c, ev.create());
+    RecordPass R;
+    if (const int rc = R.open(c, chunk)) return rc;
     SiteArgs A{};
     A.items = c->d_items.p;
     A.item_off = c->d_item_off.p;
-    A.rec = d_rec.p;
-    A.cum = d_cum.p;
-    A.infc = d_infc.p;
-    A.maf_ok = d_maf_ok.p;
+    A.rec = R.records();
+    A.cum = F.d_cum.p;
+    A.infc = F.d_infc.p;
+    A.maf_ok = F.d_maf_ok.p;
     A.limit = limit;
     A.linked_min = p->linked_min;
     A.n_sites = (uint32_t)n;
@@ -273,38 +248,31 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
     A.acc = d_acc.p;
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    const int rc = run_record_chunks(c, chunk, d_rec.p, rec_cap, &S.pairs_ms, [&](uint64_t r0, uint64_t r1, uint64_t) -> int {
-      A.out_base = c->h_row_off[r0];
-      A.r0 = r0;
-      A.r1 = r1;
-      const int rcl = launch_record_items(c, ev, r0, r1, &S.site_ms, &S.chunks, [&](const ngsld_item *items, uint64_t n_items) {
-        A.i0 = (uint64_t)(items - c->d_items.p);
-        A.i1 = A.i0 + n_items;
-        if (use_lds) {
-          const unsigned tiles = blocks_for(r1 - r0, kTileRows);
-          hipLaunchKernelGGL(site_kernel<true>, dim3(tiles), dim3(256), (size_t)words * cols * 8, st, A);
-        } else {
-          const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-          hipLaunchKernelGGL(site_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-        }
-      });
-      if (rcl != NGSLD_OK) return rcl;
+    const int rc = R.run(&S.pairs_ms, &S.site_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+      A.out_base = ch.out_base;
+      A.r0 = ch.r0;
+      A.r1 = ch.r1;
+      A.i0 = (uint64_t)(items - c->d_items.p);
+      A.i1 = A.i0 + n_items;
+      if (use_lds) {
+        const unsigned tiles = blocks_for(ch.r1 - ch.r0, kTileRows);
+        hipLaunchKernelGGL(site_kernel<true>, dim3(tiles), dim3(256), (size_t)words * cols * 8, st, A);
+      } else {
+        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+        hipLaunchKernelGGL(site_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+      }
+    }, [&](const RecordChunk &) -> int {
       unsigned long long bad = 0;
       HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      if (bad != 0) {
-        const unsigned long long k = bad - 1;
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "a site_ld value of the pair of sites " + std::to_string(k >> 32) + " - " +
-                                                  std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
-      }
-      return NGSLD_OK;
+      return bad != 0 ? fail_value_range(c, "site_ld", bad) : NGSLD_OK;
     });
     if (rc != NGSLD_OK) return rc;
     unsigned long long meta[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    if (A.track_max && meta[1] > 0 && (unsigned __int128)meta[1] * degree_max >= ((unsigned __int128)1 << 63))
+    if (A.track_max && sum_may_wrap(meta[1], degree_max))
       return fail(c, NGSLD_ERR_UNSUPPORTED, "a site in up to " + std::to_string(degree_max) + " pairs with values too large to sum exactly");
   }
 
@@ -320,18 +288,14 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
     ends += rows;
     if (rows > 0) ++S.sites_with_pairs;
     for (int v = 0; v < ns; ++v) {
-      const size_t w = 1 + 3 * (size_t)v, k = (size_t)v * n + s;
-      const int64_t sum = (int64_t)h_acc[w * n + s];
-      c->site_sum[k] = sum;
-      c->site_linked[k] = h_acc[(w + 2) * n + s];
-      if (rows == 0) {
-        c->site_max[k] = std::numeric_limits<int64_t>::min();
-        c->site_mean[k] = std::numeric_limits<double>::quiet_NaN();
-        continue;
-      }
-      c->site_max[k] = (int64_t)(h_acc[(w + 1) * n + s] - kMaxBias);
-      const double m = div_nearest((unsigned __int128)(sum < 0 ? -(__int128)sum : (__int128)sum), (unsigned __int128)rows * 1000000u);
-      c->site_mean[k] = sum < 0 ? -m : m;
+      const size_t k = (size_t)v * n + s;
+      // (no rows: nothing was added to the site's words)
+      const FieldSummary f = rows > 0 ? field_summary(h_acc.data(), n, v, s)
+                                      : FieldSummary{0, std::numeric_limits<int64_t>::min(), 0, std::numeric_limits<double>::quiet_NaN()};
+      c->site_sum[k] = f.sum;
+      c->site_max[k] = f.max;
+      c->site_linked[k] = f.linked;
+      c->site_mean[k] = f.mean;
     }
   }
   S.pairs_counted = ends / 2;

@@ -53,6 +53,11 @@ BAD = [
     (["--blocks_out=", *REGION], "--blocks_out needs a file name prefix!"),
     (["--blocks_out", "b", *REGION, "--blocks_what", "1"], "unknown option --blocks_what!"),
     (["--blocks_out", "b", "--blocks_chr"], "--blocks_chr needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    (["--blocks_out", "b", *REGION, "--blocks_ld=r3"], "--blocks_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!"),
+    (["--blocks_out", "b", *REGION, "-blocks_ld", "r3"], "--blocks_ld must be a comma-separated list of r2_ExpG, D, Dp and r2!"),
+    ([*REGION, "--", "--blocks_out", "b"], "the --blocks_* options need --blocks_out PREFIX!"),
+    (["--blocks_out", "b", *REGION, "--blocks_zzz"], "unknown option --blocks_zzz!"),
 ]
 
 

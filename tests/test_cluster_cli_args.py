@@ -62,6 +62,11 @@ BAD = [
     (["--cluster_out", "s", "--cluster_min_maf"], "--cluster_min_maf needs a value!"),
     (["--cluster_table"], "--cluster_table needs a value!"),
     (["--cluster_out"], "--cluster_out needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    (["--cluster_out", "s", "--cluster_min_maf=-0.1"], "--cluster_min_maf must be a number >= 0!"),
+    (["--cluster_out", "s", "-cluster_min_maf", "-0.1"], "--cluster_min_maf must be a number >= 0!"),
+    (["--cluster_min_maf", "0.1", "--", "--cluster_out", "s"], "the --cluster_* options need --cluster_out FILE or --cluster_table FILE!"),
+    (["--cluster_out", "s", "--cluster_zzz"], "unknown option --cluster_zzz!"),
 ]
 
 

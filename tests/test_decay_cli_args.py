@@ -55,6 +55,11 @@ BAD = [
     (["--decay_out", "b", "--decay_fit="], "--decay_fit needs a file name!"),
     (["--decay_out", "b", "--decay_what", "1"], "unknown option --decay_what!"),
     (["--decay_out", "b", "--decay_bin_size"], "--decay_bin_size needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    (["--decay_out", "b", "--decay_max_kb_dist=-1"], "--decay_max_kb_dist must be a number >= 0 (or inf)!"),
+    (["--decay_out", "b", "-decay_max_kb_dist", "-1"], "--decay_max_kb_dist must be a number >= 0 (or inf)!"),
+    (["--decay_min_maf", "0.1", "--", "--decay_out", "b"], "the --decay_* options need --decay_out FILE or --decay_fit FILE!"),
+    (["--decay_out", "b", "--decay_zzz"], "unknown option --decay_zzz!"),
 ]
 
 

@@ -206,3 +206,29 @@ def test_edge_cases_through_both_programs():
                        timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "94 through both programs, 0 differ" in r.stdout
+
+
+SLAB_FAMILIES = {
+    "prune": ["--prune_out", "k"],
+    "decay": ["--decay_out", "b"],
+    "blocks": ["--blocks_out", "b", "--blocks_chr", "1", "--blocks_start", "1", "--blocks_end", "50"],
+    "site": ["--site_out", "s"],
+    "cluster": ["--cluster_out", "s"],
+    "grid": ["--grid_out", "s", "--grid_bin_size", "100"],
+}
+
+
+@pytest.mark.parametrize("family", list(SLAB_FAMILIES))
+def test_analysis_of_a_run_cut_into_slabs_is_refused(family, tmp_path):
+    """The analyses need the whole matrix resident: a run that would go slab by slab (here by the test knob, at the shape of the
+    argument tests: no --max_gpu_mem reaches slabs at 10 sites x 4 individuals) ends in the family's refusal, nothing written."""
+    d = tmp_path
+    np.random.default_rng(1).random(10 * 4 * 3).astype("<f8").tofile(str(d / "g.bin"))
+    (d / "p.pos").write_text("".join(f"1\t{i * 10 + 1}\n" for i in range(10)))
+    r = subprocess.run([capi.CLI_PATH, "--geno", "g.bin", "--n_ind", "4", "--n_sites", "10", "--pos", "p.pos", "--max_kb_dist", "1",
+                        *SLAB_FAMILIES[family]], capture_output=True, text=True, cwd=str(d), timeout=120,
+                       env=dict(os.environ, NGSLD_TEST_SLAB_SITES="5"))
+    assert r.returncode == 255, (r.returncode, r.stderr[-500:])
+    assert (f"ERROR: [main] --{family}_out needs the whole matrix resident on one device: it does not fit (--max_gpu_mem) and would be "
+            "cut into slabs!") in r.stderr, r.stderr[-500:]
+    assert sorted(os.listdir(d)) == ["g.bin", "p.pos"]

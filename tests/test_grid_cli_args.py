@@ -63,6 +63,11 @@ BAD = [
     ([*G, "--grid_signed=1"], "unknown option --grid_signed!"),
     ([*G, "--grid_min_maf"], "--grid_min_maf needs a value!"),
     (["--grid_bin_size", "100", "--grid_out"], "--grid_out needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    ([*G, "--grid_min_maf=-0.1"], "--grid_min_maf must be a number >= 0!"),
+    ([*G, "-grid_min_maf", "-0.1"], "--grid_min_maf must be a number >= 0!"),
+    (["--grid_bin_size", "100", "--", "--grid_out", "s"], "the --grid_* options need --grid_out FILE!"),
+    ([*G, "--grid_zzz"], "unknown option --grid_zzz!"),
 ]
 
 

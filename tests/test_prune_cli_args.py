@@ -46,6 +46,11 @@ BAD = [
     (["--prune_out="], "the --prune_* options need --prune_out FILE!"),
     (["--prune_out", "k", "--prune_what", "1"], "unknown option --prune_what!"),
     (["--prune_out", "k", "--prune_field"], "--prune_field needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    (["--prune_out", "k", "--prune_max_kb_dist=-1"], "--prune_max_kb_dist must be a number >= 0 (or inf)!"),
+    (["--prune_out", "k", "-prune_max_kb_dist", "-1"], "--prune_max_kb_dist must be a number >= 0 (or inf)!"),
+    (["--prune_min_weight", "0.1", "--", "--prune_out", "k"], "the --prune_* options need --prune_out FILE!"),
+    (["--prune_out", "k", "--prune_zzz"], "unknown option --prune_zzz!"),
 ]
 
 

@@ -49,6 +49,11 @@ BAD = [
     (["--site_out", "s", "--site_signed=1"], "unknown option --site_signed!"),
     (["--site_out", "s", "--site_min_maf"], "--site_min_maf needs a value!"),
     (["--site_out"], "--site_out needs a value!"),
+    # the forms a flag can take on the command line: --name=value, one dash, after "--" (left to getopt: not taken)
+    (["--site_out", "s", "--site_min_maf=-0.1"], "--site_min_maf must be a number >= 0!"),
+    (["--site_out", "s", "-site_min_maf", "-0.1"], "--site_min_maf must be a number >= 0!"),
+    (["--site_min_maf", "0.1", "--", "--site_out", "s"], "the --site_* options need --site_out FILE!"),
+    (["--site_out", "s", "--site_zzz"], "unknown option --site_zzz!"),
 ]
 
 
