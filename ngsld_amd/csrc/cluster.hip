@@ -178,7 +178,7 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
   for (uint64_t s = 0; s < n; ++s) parent[s] = (uint32_t)s;
   unsigned long long meta[2] = {0, 0};
   // every partial sum of a cluster is exact while max |q| * its edges < 2^63: certain below 2^25 edges (|q| < 2^38)
-  const bool track_max = n_pairs >= (1ull << 25);
+  const bool track_max = track_sums(n_pairs >= (1ull << 25));
   if (n_pairs > 0) {
     DevBuf<uint32_t> d_parent;
     DevBuf<uint8_t> d_node;
@@ -265,12 +265,15 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
   K.span.resize(nk);
   K.mean.resize(nk);
   K.density.resize(nk);
+  {  // the cluster of the most edges bounds every other's sums: the refusal names it
+    const uint64_t most = nk ? *std::max_element(K.edges.begin(), K.edges.end()) : 0;
+    if (track_max && track_sums(most >= (1ull << 25)) && sum_may_wrap(meta[1], most)) {
+      c->clear_clusters();
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(most) + " edges with values too large to sum exactly");
+    }
+  }
   for (size_t k = 0; k < nk; ++k) {
     const uint64_t size = K.size[k], edges = K.edges[k];
-    if (track_max && edges >= (1ull << 25) && sum_may_wrap(meta[1], edges)) {
-      c->clear_clusters();
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(edges) + " edges with values too large to sum exactly");
-    }
     S.edges += edges;
     if (size >= 2) ++S.clusters_multi;
     S.largest = std::max<uint64_t>(S.largest, size);

@@ -35,7 +35,7 @@ struct BinArgs {
   uint32_t n_slots;           // bins 0 .. n_slots-1
   int ns;                     // chosen fields
   int field[4];               // 0 r2_ExpG, 1 D, 2 D', 3 r2
-  int track_max;              // a chunk of more than kRecordChunkPairs pairs: max |q| goes to meta[1]
+  int track_max;              // a chunk of more pairs than the pass's chunk (one row): max |q| goes to meta[1]
   unsigned long long *acc;    // [(1 + ns) * n_slots]: rows per bin, then the int64 sums of each field (two's complement)
   unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|, [2] a bin beyond n_slots
 };
@@ -250,7 +250,7 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
     std::vector<unsigned long long> h_acc(W);
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
     const int rc = R.run(&S.pairs_ms, &S.bin_ms, &S.chunks, [&](const RecordChunk &ch) -> int {
-      A.track_max = ch.pairs > kRecordChunkPairs ? 1 : 0;
+      A.track_max = track_sums(ch.pairs > chunk) ? 1 : 0;
       HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
       return NGSLD_OK;
     }, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {

@@ -1120,7 +1120,9 @@ int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const
         if (rc != NGSLD_OK) return rc;
       }
       const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-      const uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
+      uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
+      if (const char *e = test_knob("RECORD_SLICE_ITEMS"))  // tests: a chunk's items in many launches
+        max_items = std::min<uint64_t>(max_items, std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)));
       HIP_TRY(c, hipEventRecord(ev.a, c->stream));
       for (uint64_t off = i0; off < i1; off += max_items) {
         launch(ch, c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));

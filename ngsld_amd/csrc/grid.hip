@@ -372,7 +372,7 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
     for (int v = 0; v < 4; ++v) A.field[v] = field[v];
     A.abs_value = p->abs_value != 0 ? 1 : 0;
     // every partial sum of a cell is exact while max |q| * (the rows it can hold) < 2^63: certain below 2^25 rows (|q| < 2^38)
-    A.track_max = cell_rows >= (1ull << 25) ? 1 : 0;
+    A.track_max = track_sums(cell_rows >= (1ull << 25)) ? 1 : 0;
     A.acc = d_acc.p;
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;

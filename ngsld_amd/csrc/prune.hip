@@ -310,7 +310,8 @@ int ngsld_prune(ngsld_ctx *c, const ngsld_prune_params *p, const char *const *la
   DevBuf<uint32_t> d_ea, d_eb;
   DevBuf<int64_t> d_el;
   RecordPass R;  // (a row longer than the chunk is refused)
-  if (const int rc = R.open(c, std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, kRecordChunkPairs)), nullptr, false)) return rc;
+  const uint64_t chunk = record_chunk(test_knob("PRUNE_CHUNK_PAIRS"));
+  if (const int rc = R.open(c, std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, chunk)), nullptr, false)) return rc;
   EdgeArgs A{};
   A.field = p->field - 4;
   A.cum = F.d_cum.p;

@@ -83,8 +83,9 @@ struct RecordPass {
   int open(ngsld_ctx *c, uint64_t chunk_pairs, const uint8_t *rows = nullptr, bool fit_longest_row = true);
   // Every chunk: ngsld_run_device + ngsld_finish_device on the context's stream, so every record is final (replayed pairs carry
   // their replayed values); before; launch for each slice of the chunk's items, every slice below 2^32 threads at one wavefront
-  // per item, all of them between two events; the wait for the second; then after.  *pairs_ms adds the wall time of the pair
-  // phase, *kernel_ms the events' span, *chunks (when not null) counts the chunks.
+  // per item (2^24 items, or NGSLD_TEST_RECORD_SLICE_ITEMS if that is fewer), all of them between two events; the wait for the
+  // second; then after.  *pairs_ms adds the wall time of the pair phase, *kernel_ms the events' span, *chunks (when not null)
+  // counts the chunks.
   int run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const Step &before, const Launch &launch, const Step &after = nullptr);
   ngsld_rec_std *records() const { return d_rec.p; }
   void close() { d_rec.release(); }
@@ -113,9 +114,15 @@ int fail_value_range(ngsld_ctx *c, const char *pass, unsigned long long meta0);
 
 // Sums of integer micro-units are exact while max |q| * (the rows of a sum) < 2^63: certain below 2^25 rows (|q| < 2^38), where
 // the kernels do not track max |q| at all.  True when a sum of `rows` values of up to max_q may have wrapped.
+// NGSLD_TEST_SUM_WRAP_LIMIT = L (tests; 1 <= L <= 2^63): the limit is L instead of 2^63, and track_sums holds whatever the
+// job's size, so that a small job runs the tracking of a large one and the kernels' max |q| can be pinned to the unit.
 inline bool sum_may_wrap(unsigned long long max_q, uint64_t rows) {
-  return max_q > 0 && (unsigned __int128)max_q * rows >= ((unsigned __int128)1 << 63);
+  unsigned __int128 limit = (unsigned __int128)1 << 63;
+  if (const char *e = test_knob("SUM_WRAP_LIMIT")) limit = std::max<uint64_t>(1, std::min<uint64_t>(1ull << 63, std::strtoull(e, nullptr, 10)));
+  return max_q > 0 && (unsigned __int128)max_q * rows >= limit;
 }
+// whether a pass tracks max |q|: `large` is its own condition (a sum of 2^25 rows or more, a row longer than a chunk)
+inline bool track_sums(bool large) { return large || test_knob("SUM_WRAP_LIMIT") != nullptr; }
 
 // One entry of the accumulators of ngsld_site_ld and ngsld_grid, acc[1 + 3 * fields][n] (rows; then per field the int64 sum in
 // two's complement, the biased maximum, the linked rows): field v of entry k, which has rows > 0.  The mean is the double nearest

@@ -244,7 +244,7 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
     for (int v = 0; v < 4; ++v) A.field[v] = field[v];
     A.abs_value = p->abs_value != 0 ? 1 : 0;
     // every partial sum of a site is exact while max |q| * (the rows it can be in) < 2^63: certain below 2^25 rows (|q| < 2^38)
-    A.track_max = degree_max >= (1ull << 25) ? 1 : 0;
+    A.track_max = track_sums(degree_max >= (1ull << 25)) ? 1 : 0;
     A.acc = d_acc.p;
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;

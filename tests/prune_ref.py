@@ -109,10 +109,16 @@ def label_order(labels: list[str]) -> list[int]:
     return rank
 
 
-def prune_tsv(text: str, keep_heavy: bool = False, **kw) -> tuple[set[str], set[str]]:
-    """(kept, excluded) labels of an ngsLD TSV, as prune_graph.pl prints them (as sets)."""
+def prune_tsv_counts(text: str, keep_heavy: bool = False, **kw) -> tuple[set[str], set[str], int, int]:
+    """(kept, excluded, nodes, edges) of an ngsLD TSV: prune_tsv's sets, and how many nodes and edges (rows that pass the edge
+    filter: a pair is one row of the table) the graph they were pruned from has."""
     nodes, edges = tsv_graph(text, **kw)
     names = list(nodes)
     index = {lab: i for i, lab in enumerate(names)}
     excl = prune_sequential(len(names), [(index[a], index[b], lab) for a, b, lab in edges], keep_heavy, label_order(names))
-    return {names[i] for i in range(len(names)) if i not in excl}, {names[i] for i in excl}
+    return {names[i] for i in range(len(names)) if i not in excl}, {names[i] for i in excl}, len(names), len(edges)
+
+
+def prune_tsv(text: str, keep_heavy: bool = False, **kw) -> tuple[set[str], set[str]]:
+    """(kept, excluded) labels of an ngsLD TSV, as prune_graph.pl prints them (as sets)."""
+    return prune_tsv_counts(text, keep_heavy, **kw)[:2]

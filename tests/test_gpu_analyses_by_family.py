@@ -12,9 +12,10 @@ What the restatements cannot see -- they read the engine's TSV, so an item dropp
 is checked apart from the engine: the TSV's (site1, site2, dist) columns against a plain enumeration of the window, and some
 20 rows per multi-wavefront and streaming case against the oracle's own records of the two sites.
 
-LD pruning has no chunk knob: ngsld_prune cuts its record pass at kRecordChunkPairs (2^24 pairs, engine.h), a constant no
-tuning call or test knob reaches, so it stays at one chunk here (its chunk loop is run_record_chunks, the one the four other
-passes go through in several chunks).
+LD pruning's chunk loop is under test too: NGSLD_TEST_PRUNE_CHUNK_PAIRS cuts its record pass (RecordPass, the one the other
+passes go through) at a tenth of the pairs in the chunk cuts below, where site_state keeps its bytes and is held to prune_ref
+again; its stats carry no chunk count, so that it ran in chunks is shown in tests/test_gpu_record_pass_large.py, from the pairs
+of the last ngsld_run_device, with the edge arrays regrown from chunk to chunk and the refusal of a row beyond the chunk.
 
 GPU time of this file on one MI355X: see README.md (the tests row)."""
 import functools
@@ -43,7 +44,8 @@ LIMIT = 20_000
 PRUNE_KW = dict(min_weight=0.3, weight_type="a")  # (test_gpu_prune.py's floor from 500 individuals on)
 DECAY_KW = dict(ld=ALL4, bin_size=33.3)
 SITE_KW = dict(ld=ALL4, abs_value=False, linked_min=0.3)
-CHUNK_KNOBS = ("NGSLD_TEST_DECAY_CHUNK_PAIRS", "NGSLD_TEST_SITE_CHUNK_PAIRS", "NGSLD_TEST_CLUSTER_CHUNK_PAIRS")
+CHUNK_KNOBS = ("NGSLD_TEST_DECAY_CHUNK_PAIRS", "NGSLD_TEST_SITE_CHUNK_PAIRS", "NGSLD_TEST_CLUSTER_CHUNK_PAIRS",
+               "NGSLD_TEST_PRUNE_CHUNK_PAIRS")
 KNOBS = CHUNK_KNOBS + ("NGSLD_TEST_BLOCKS_CHUNK_PAIRS", "NGSLD_TEST_SITE_LDS_BYTES", "NGSLD_TEST_DECAY_LDS_BYTES",
                        "NGSLD_TEST_BLOCKS_HOST_ROWS", "NGSLD_TEST_BLOCKS_TEXT_ROWS")
 SPOT_PAIRS, SPOT_SEED = 20, 5
@@ -188,7 +190,7 @@ def _check_prune(s, res):
     assert got_kept == kept and got_excl == excl, (len(got_kept ^ kept), len(got_excl ^ excl))
     assert stats["nodes"] == stats["kept"] + stats["excluded"] == len(kept) + len(excl)
     assert stats["pairs"] == s.n_pairs and stats["edges"] > 0 and stats["excluded"] > 0
-    return f"prune: pairs {stats['pairs']} nodes {stats['nodes']} edges {stats['edges']} excluded {stats['excluded']} chunks 1"
+    return f"prune: pairs {stats['pairs']} nodes {stats['nodes']} edges {stats['edges']} excluded {stats['excluded']}"
 
 
 def _run_decay(s):
@@ -389,7 +391,8 @@ def test_cut_small_gives_the_same_bytes(cut, monkeypatch):
     """pairs_per_item 5: items of 20 candidates under the multi-wavefront kernel and of 5 under the streaming kernel, no row a
     whole number of them, no item as wide as a wavefront.  Chunks: a tenth of the pairs a chunk (of the region's rows' pairs for
     the blocks), and the site-LD pass once with its LDS tiles and once with global atomics.  Plan, TSV and every result keep
-    their bytes, and the results are held to the restatements again.  (Pruning has no chunk knob: see the module's text.)"""
+    their bytes, and the results are held to the restatements again.  (Pruning is cut in chunks too; its stats count none: see the
+    module's text.)"""
     name, ppi, chunks = CUTS[cut]
     input_name, how, kernel, _, span16 = CASES[name]
     for k in KNOBS:
