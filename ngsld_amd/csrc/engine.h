@@ -268,6 +268,9 @@ struct ngsld_ctx {
   PairConfig cfg{};
   bool have_geno = false;
   DevBuf<double> d_planes, d_maf, d_mean, d_rsx, d_sc4;
+  // [n_sites] sums of the sites' posterior dosages (ld_prep.hip, site_dose_kernel): there only where the run kernel takes each
+  // pair's first EM step from them -- every individual counting, two to eight slots (NGSLD_TEST_FIRST_STEP=0: nowhere)
+  DevBuf<double> d_dose_sum;
   DevBuf<int> d_status;
   std::vector<double> h_maf, h_pos_dist;
   // hard-called matrices (kHard): per-site genotype bit sets

@@ -61,6 +61,7 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
   a.row1 = (uint32_t)r1;
   a.planes_bytes = c->n_sites * 3ull * c->np * sizeof(double);
   a.sc4 = c->d_sc4.p;
+  a.dose_sum = c->cfg.kernel == kRun ? c->d_dose_sum.p : nullptr;
   a.out_base = c->h_row_off[r0];
   a.out_std = d_std;
   a.out_ext = d_ext;

@@ -144,6 +144,10 @@ struct PairArgs {
   const uint64_t *h_item_off;  // the same on the host (for the launcher; never dereferenced on the device)
   uint32_t row0, row1, tile_rows, tile_nk;
   uint64_t planes_bytes;       // size of the whole planes array (launcher: is the matrix larger than the caches?)
+  // first EM step from the sites' posterior dosages (run kernel, every individual counts, two to eight slots: ld_kernel_run.h).
+  // [n_sites] the sum of a site's dosages under its own labels (site_dose_kernel, ld_prep.hip); negative: the site takes no
+  // part (not dose_ok).  Null: every pair starts at iteration 0 with the per-individual step.
+  const double *dose_sum;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -280,6 +284,28 @@ __device__ __forceinline__ double rcp_refined(double s) {
   const double e = fma(-s, r0, 1.0);
   const double t = fma(e, e, e);
   return fma(r0, t, r0);
+}
+
+// Posterior dosage of one individual at one site under HWE weights u(m) = ((1-m)^2, 2m(1-m), m^2): d = num / den with
+// den = u . a and num = u1 a1 + 2 u2 a2.  ONE order of operations for everyone who forms them -- the per-site sums and
+// flags (site_dose_kernel, ld_prep.hip) and the run kernel's row and candidate sides -- so that a den the prep found positive
+// and finite is the very double the kernel divides by:  t = u1 a1;  den = fma(u2, a2, fma(u0, a0, t));  num = fma(2 u2, a2, t).
+struct DoseWeights {
+  double u0, u1, u2, u2x2;
+};
+__device__ __forceinline__ DoseWeights dose_weights(double m) {
+  const double q = 1.0 - m;
+  DoseWeights u;
+  u.u0 = q * q;
+  u.u1 = 2.0 * (m * q);
+  u.u2 = m * m;
+  u.u2x2 = 2.0 * u.u2;
+  return u;
+}
+__device__ __forceinline__ void dose_terms(const DoseWeights &u, double a0, double a1, double a2, double &den, double &num) {
+  const double t = u.u1 * a1;
+  den = fma(u.u2, a2, fma(u.u0, a0, t));
+  num = fma(u.u2x2, a2, t);
 }
 
 // Workgroup barrier that orders LDS traffic only: s_waitcnt lgkmcnt(0) + s_barrier.  __syncthreads() would also

@@ -193,12 +193,17 @@ __device__ __forceinline__ uint32_t count_valid(uint32_t vbits) {
 // outcome -- is caught by the sanity test on the new frequencies, after which the iteration is redone with one reciprocal
 // per individual before anything is concluded from it.  (One reciprocal per individual, and one per two individuals, were
 // the earlier forms: -9 % and -4 % against the tree at eight slots.)
-template <int SLOTS, int WAVES>
+//   FIRST:     (run kernel) iteration 0's new frequencies may come from outside -- have0 (wave-uniform), g1..g3 = hap 1..3
+//              of the step from linkage equilibrium, taken from the sites' posterior dosages (ld_kernel_run.h) -- and the
+//              hot loop is then entered at iteration 1
+template <int SLOTS, int WAVES, bool FIRST = false>
 __device__ __forceinline__ uint32_t em_pair(const double (&P)[SLOTS][9], uint32_t vbits, double inv_x, double m1,
                                             double m2, double &f0, double &f1, double &f2, double &f3,
                                             double (*xch)[WAVES][4], int sub, int lane, int *status,
-                                            uint32_t *xpar = nullptr) {
+                                            uint32_t *xpar = nullptr, bool have0 = false, double g1 = 0.0,
+                                            double g2 = 0.0, double g3 = 0.0) {
   static_assert(WAVES == 1 || WAVES == 2 || WAVES == 4 || WAVES == 8, "em_pair: 1, 2, 4 or 8 wavefronts per pair");
+  static_assert(!FIRST || (WAVES == 1 && SLOTS > 1), "em_pair: a given first step is the run kernel's");
   f0 = (1 - m1) * (1 - m2); f1 = (1 - m1) * m2; f2 = m1 * (1 - m2); f3 = m1 * m2;  // gen_func.cpp:1034-1037
   if (m1 < 0 || m1 > 1 || m2 < 0 || m2 > 1) {  // error() in the reference (:1030); reported through status
     if (lane == 0 && sub == 0) atomicExch(status, (int)NGSLD_ERR_MAF_RANGE);
@@ -346,6 +351,33 @@ __device__ __forceinline__ uint32_t em_pair(const double (&P)[SLOTS][9], uint32_
   constexpr double kFullBelow = 0x1p-10;
   bool full = __builtin_amdgcn_ballot_w64(f0 < kFullBelow) != 0;  // wave-uniform (f is)
   bool done = false;
+  if constexpr (FIRST) {
+    // Iteration 0 with its new frequencies given: the three-value form's n0 and the hot loop's bookkeeping, expression for
+    // expression.  New frequencies that do not look sane are dropped, and the pair starts at iteration 0 below as it does
+    // without them (the per-individual step and, if that one is odd too, its second opinion).
+    // (One case is not the reference's: an individual whose two dens are positive and finite each -- dose_ok -- while their
+    // product, the reference's s, underflows to 0: there every tmp/sum is NaN and nIter 0, here the given step is finite and
+    // counts as iteration 0.  It takes frequencies around 1e-80 handed in through ngsld_set_geno_lkl.)
+    if (have0 && !full) {
+      const double n1 = g1, n2 = g2, n3 = g3;
+      const double n0 = 1.0 - ((n1 + n2) + n3);
+      if (!__builtin_amdgcn_ballot_w64(!(n1 < 2.0))) {
+        bool conv = false;
+        if (__builtin_amdgcn_ballot_w64(fabs(n1 - f1) < kEpsilonTie)) {
+          const double eps = fmax(fmax(fabs(n0 - f0), fabs(n1 - f1)), fmax(fabs(n2 - f2), fabs(n3 - f3)));
+          conv = __builtin_amdgcn_ballot_w64(eps < kEpsilon) != 0;  // gen_func.cpp:1054-1055
+          tie |= __builtin_amdgcn_ballot_w64(fabs(eps - kEpsilon) < kTieMargin) != 0;
+        }
+        f0 = n0; f1 = n1; f2 = n2; f3 = n3;
+        if (conv) {
+          done = true;
+        } else {
+          if (__builtin_amdgcn_ballot_w64(n0 < kFullBelow)) full = true;
+          n_iter = 1;  // this iteration is complete
+        }
+      }
+    }
+  }
   while (!done && n_iter < (uint32_t)kIterMax) {
     if constexpr (kTree) {
       if (!full) {

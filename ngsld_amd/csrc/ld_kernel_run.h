@@ -10,6 +10,35 @@ namespace ngsld {
 // sc4[.][3] by site_skip_kernel, ld_prep.hip -- is staged for its Pearson moment only; its frequencies are left NaN, which
 // write_pair flags, and the exact-order replay is the pair's one evaluation (it was going to start the pair over anyway).  A
 // variant of its own so that launches over SNP-called matrices keep the instruction stream they had.
+//
+// FIRST STEP FROM DOSAGES (kFirst: every individual counts, two to eight slots; on where PairArgs::dose_sum is set).  Every
+// pair starts at linkage equilibrium, f = (1-m1, m1) x (1-m2, m2), where the two-locus genotype weights factorise: an
+// individual's posterior over the nine genotype pairs is alpha_g beta_h, with alpha_g = u_g a_g / (u . a),
+// u = ((1-m)^2, 2m(1-m), m^2), a matter of site 1 alone, and a double heterozygote is cis or trans with probability 1/2.
+// With the posterior dosage d = alpha_1 + 2 alpha_2 the expected count of haplotype (1,1) is d1 d2 / 2, so iteration 0 is
+//   f3' = S12 / (4n),  f2' = S1 / (2n) - f3',  f1' = S2 / (2n) - f3',  f0' = 1 - ((f1' + f2') + f3'),   S12 = sum d1 d2, S = sum d.
+// S is a per-site scalar, summed once per matrix by site_dose_kernel (ld_prep.hip), which also says whether the site may
+// take part (dose_ok).  The row's dosages are formed once per run, from its planes in LDS, and stay in LDS (4 KB at eight
+// slots).  The candidate's are formed from its planes right before stage_pair turns them into P: den and num per slot, ONE
+// reciprocal per lane for all its slots (RcpTree), one FMA per slot into S12 -- 6 instructions per slot and the tree,
+// against the step's 17 and its tree, contraction and three-value reduction.  (A dose array beside the planes, each
+// candidate's 4 KB brought in with its site copy, was built first and has no place to land: four more 4 KB buffers make
+// 88 KB of LDS where 80 KB let two workgroups share a CU, and the kernel has not one VGPR to spare -- with eight doubles per
+// lane held a pair ahead the cross-compile spilled 28, and any product hoisted out of the pair loop spills as well: see
+// the note at g1 .. g3.)
+// S12 has a REDUCTION OF ITS OWN, a second wave_sum1_bcast in front of stage_pair: six DPP adds and a readlane more per pair
+// than one pass for both sums would take.  The lane's share of S12 is complete before P exists, that of the Pearson moment
+// only after it; carried across stage_pair as a VGPR pair and reduced beside the moment (the same DPP steps, interleaved),
+// the cross-compile spills 2 VGPRs to scratch at eight slots.  The total is wavefront-uniform and crosses in SGPRs.  The
+// moment's own reduction -- and with it r2_ExpG -- is what it was.
+// The candidate's S comes through the scalar cache, behind stage_pair (see there).  Everything is formed under the
+// kernel's labels (Relabel), so no sum needs turning round.  A pair with a site that is not dose_ok, or whose given
+// frequencies fail em_pair's sanity test (a product of dens that underflowed: NaN), starts at iteration 0 as before; the
+// choice is wavefront-uniform, and under a row that is not dose_ok no candidate forms its dosages.  Nine and ten slots have no LDS left
+// for the row's dosages and spill already: they keep the per-individual first step.  The SKIP variant takes the step like
+// the plain one: which of the two a launch gets depends on the context (marks on or off, a replay that can take the marked
+// pairs), and the pairs both compute must come out the same bits in both (tests/test_gpu_replay_lkl.py,
+// tests/test_gpu_multi_native.py).
 template <int SLOTS, bool MASKED, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   constexpr int kSiteBytes = SLOTS * 64 * 3 * 8;
@@ -19,7 +48,10 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   constexpr uint32_t kRing = SLOTS <= 9 ? 32 : 8;
   constexpr int kRingOff = kSiteBytes + 4 * kBuf;
   constexpr int kListOff = kRingOff + 4 * (int)(kRing * sizeof(RunResult));
-  __shared__ __attribute__((aligned(16))) char smem[kListOff + sizeof(RunList)];
+  constexpr bool kFirst = !MASKED && SLOTS >= 2 && SLOTS <= 8;
+  constexpr int kDoseOff = kListOff + (int)sizeof(RunList);  // (kFirst) the row's dosages, [kNp] doubles
+  static_assert(sizeof(RunList) % 8 == 0, "run kernel: doubles behind the run list");
+  __shared__ __attribute__((aligned(16))) char smem[kDoseOff + (kFirst ? (int)kNp * 8 : 0)];
   static_assert(sizeof(smem) <= 81920, "run kernel: two workgroups per CU need <= 80 KB of LDS each");
 
   const int lane = threadIdx.x & 63;
@@ -41,6 +73,22 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   const uint32_t n_kept = (uint32_t)__builtin_amdgcn_readfirstlane((int)L->base[run.n_items]);
   const uint32_t s2_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)L->items[0].s2_begin);
   const uint64_t rec_base = g_items[0].first_record - A.out_base;
+  const bool first_on = kFirst && A.dose_sum != nullptr;  // (a kernel argument: wavefront-uniform)
+  double S1 = -1.0;
+  if (first_on) {
+    S1 = uniform(A.dose_sum[s1]);
+    S1 = uniform(S1 < 0.0 ? S1 : 0.5 * S1);  // half the sum is what the pairs use (in SGPRs)
+    const bool flip1 = m1 > 0.5;  // (Relabel: the row's labels are the same for all its pairs)
+    const DoseWeights u = dose_weights(flip1 ? 1.0 - m1 : m1);
+    const double *pa = reinterpret_cast<const double *>(lds_a);
+    double *d1 = reinterpret_cast<double *>(smem + kDoseOff);
+    for (uint32_t i = threadIdx.x; i < kNp; i += 256) {
+      double den, num;
+      dose_terms(u, pa[(flip1 ? 2 * kNp : 0u) + i], pa[kNp + i], pa[(flip1 ? 0u : 2 * kNp) + i], den, num);
+      d1[i] = i < A.n_ind ? num / den : 0.0;  // (a row that is not dose_ok: whatever this gives is never used)
+    }
+    __syncthreads();
+  }
 
   // one computed pair of the run: site and record index
   struct Cand {
@@ -82,6 +130,25 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     uint32_t vbits;
     double sxy;
     const Relabel rl = relabel(m1, m2, mean1, mean2);
+    double s12 = 0.0;
+    const bool dose1 = first_on && !skip && S1 >= 0.0;  // (wavefront-uniform) the row is dose_ok
+    if (dose1) {  // this lane's share of sum d1 d2, before P takes the registers
+      const DoseWeights u = dose_weights(rl.m2);
+      const double *d1 = reinterpret_cast<const double *>(smem + kDoseOff) + lane;
+      const double *pb = reinterpret_cast<const double *>(lds_b) + lane;
+      double den[SLOTS], numd[SLOTS], rv[SLOTS];
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j) {
+        double num;
+        dose_terms(u, pb[(rl.flip2 ? 2 * kNp : 0u) + 64 * j], pb[kNp + 64 * j], pb[(rl.flip2 ? 0u : 2 * kNp) + 64 * j], den[j], num);
+        if (j == SLOTS - 1 && (uint32_t)lane + 64u * j >= A.n_ind) den[j] = 1.0;  // a padding lane: planes and d1 are 0
+        numd[j] = num * d1[64 * j];
+      }
+      RcpTree<SLOTS>::down(den, rcp_refined(RcpTree<SLOTS>::prod(den)), rv);  // one reciprocal for the lane's slots
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j) s12 = fma(numd[j], rv[j], s12);  // in slot order
+      s12 = wave_sum1_bcast(s12);
+    }
     stage_pair<SLOTS, MASKED, !MASKED, true>(reinterpret_cast<const double *>(lds_a), kNp, (uint32_t)lane,
                                              reinterpret_cast<const double *>(lds_b), kNp, (uint32_t)lane, (uint32_t)lane,
                                              A.n_ind, rl.mean1, rl.mean2, P, vbits, sxy, rl.flip1, rl.flip2);
@@ -90,11 +157,39 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     if (nxt.ok) dma_site(nxt.s2);
     const uint32_t x = MASKED ? count_valid<SLOTS>(vbits) : A.n_ind;
     const double inv_x = MASKED ? 1.0 / (double)x : A.inv_n;
+    // The candidate's dosage sum, through the SCALAR cache: the address is wavefront-uniform, and a vector load here would
+    // come back behind the 12 KB of the next site's copy just issued (loads return in order) and have that copy -- meant to
+    // fly through the whole EM loop -- waited for as well.  Assembly, because the compiler makes a vector load of it (the
+    // kernel writes global memory); issued here, waited for after the Pearson moment's reduction.
+    // (The empty statement pins the lane's share of the moment in front of the load: the compiler's own wait for
+    // stage_pair's LDS reads, which it places at their first use, would otherwise come right behind the load.)
+    double S2 = -1.0;
+    if constexpr (kFirst) {
+      asm volatile("" : "+v"(sxy));
+      if (dose1) asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(S2) : "s"(A.dose_sum + cur.s2) : "memory");
+    }
     sxy = fma(-(double)A.n_ind * rl.mean1, rl.mean2, wave_sum1_bcast(sxy));  // centred: sum e1 e2 - n mean1 mean2
+    if constexpr (kFirst) {
+      if (dose1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(S2)::"memory");
+    }
     double f0, f1, f2, f3;
     uint32_t n_iter = 0;
     if (skip) {  // (wavefront-uniform)
       f0 = f1 = f2 = f3 = __builtin_nan("");
+    } else if constexpr (kFirst) {
+      bool have0 = false;
+      double g1 = 0.0, g2 = 0.0, g3 = 0.0;
+      if (dose1) {
+        have0 = S2 >= 0.0;  // both sites dose_ok
+        // (written so that nothing here is invariant over the run's pairs: a hoisted product is a VGPR pair held through every
+        // EM loop, and the kernel has none to give)
+        g3 = (0.25 * s12) * inv_x;
+        g2 = S1 * inv_x - g3;
+        g1 = (0.5 * S2) * inv_x - g3;
+      }
+      n_iter = em_pair<SLOTS, 1, true>(P, vbits, inv_x, rl.m1, rl.m2, f0, f1, f2, f3, (double (*)[1][4]) nullptr, 0, lane,
+                                       A.status, nullptr, have0, g1, g2, g3);
+      unrelabel(rl.flip1, rl.flip2, f0, f1, f2, f3);
     } else {
       n_iter = em_pair<SLOTS, 1>(P, vbits, inv_x, rl.m1, rl.m2, f0, f1, f2, f3, (double (*)[1][4]) nullptr, 0, lane, A.status);
       unrelabel(rl.flip1, rl.flip2, f0, f1, f2, f3);

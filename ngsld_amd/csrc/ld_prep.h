@@ -51,6 +51,10 @@ hipError_t launch_pack_scalars(const double *maf, const double *mean_e, const do
 // the pair kernels leave their EM out); *count (preset to 0) = how many
 hipError_t launch_site_skip(const double *planes, uint64_t site_stride, uint32_t np, uint32_t n_ind, int ignore_miss, const double *maf,
                             uint64_t n_sites, uint8_t *skip, uint32_t *count, hipStream_t stream);
+// dose_sum[s] = the sum of site s's posterior dosages, or -1 where the site is not dose_ok: the per-site half of the run kernel's
+// first EM step (ld_kernel_run.h).  maf: what goes into sc4[.][0]; skip (may be null): site_skip_kernel's marks
+hipError_t launch_site_dose(const double *planes, uint64_t site_stride, uint32_t np, uint32_t n_ind, const double *maf, const uint8_t *skip,
+                            uint64_t n_sites, double *dose_sum, hipStream_t stream);
 hipError_t launch_selftest(const double *in, double *out, hipStream_t stream);
 
 }  // namespace ngsld

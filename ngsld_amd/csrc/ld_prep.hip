@@ -487,6 +487,52 @@ hipError_t launch_pack_scalars(const double *maf, const double *mean_e, const do
   return hipGetLastError();
 }
 
+// The per-site half of the run kernel's first EM step from dosages (ld_kernel_run.h): dose_sum[s] = sum_i d_i, the posterior
+// dosages of the site's individuals under HWE weights at the site's frequency -- the very double that goes into sc4[.][0], under
+// the labels the pair kernels give the site (Relabel: a frequency above 1/2 is 1 - m with planes 0 and 2 trading places) -- or
+// -1 where the site is not dose_ok and its pairs keep the per-individual first step:
+//   * the frequency is not strictly inside (0, 1);
+//   * some individual's den = u . a (dose_terms: the kernel's own order of operations) is <= 0 or not finite, or its dosage is
+//     not finite;
+//   * a triple does not sum to 1 (odd_triple: what signed_rsx looks for, at either label);
+//   * site_skip_kernel marked the site degenerate.
+// One wavefront per site; the sum in a FIXED order: a lane's individuals in slot order, then wave_sum1 over the lanes.
+__global__ __launch_bounds__(256) void site_dose_kernel(const double *__restrict__ planes, uint64_t site_stride, uint32_t np, uint32_t n_ind,
+                                                        const double *__restrict__ maf, const uint8_t *__restrict__ skip, uint64_t n_sites,
+                                                        double *__restrict__ dose_sum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (uint64_t site = (uint64_t)blockIdx.x * 4 + wave; site < n_sites; site += (uint64_t)gridDim.x * 4) {
+    const double *pl = planes + site * site_stride;
+    const double m_in = maf[site];
+    const bool flip = m_in > 0.5;
+    const double m = flip ? 1.0 - m_in : m_in;
+    const DoseWeights u = dose_weights(m);
+    const double *p0 = pl + (flip ? 2ull * np : 0ull), *p1 = pl + np, *p2 = pl + (flip ? 0ull : 2ull * np);
+    bool ok = m_in > 0.0 && m_in < 1.0 && !(skip != nullptr && skip[site]);
+    double acc = 0.0;
+    for (uint32_t i = (uint32_t)lane; i < n_ind; i += 64) {
+      const double a0 = p0[i], a1 = p1[i], a2 = p2[i];
+      double den, num;
+      dose_terms(u, a0, a1, a2, den, num);
+      const double d = num / den;
+      ok = ok && den > 0.0 && den < __builtin_inf() && d >= 0.0 && d < __builtin_inf() && !odd_triple(a0, a1, a2);
+      acc += d;
+    }
+    const double S = wave_sum1(acc);
+    const bool all_ok = __ballot(!ok) == 0 && S >= 0.0 && S < __builtin_inf();
+    if (lane == 0) dose_sum[site] = all_ok ? S : -1.0;
+  }
+}
+
+hipError_t launch_site_dose(const double *planes, uint64_t site_stride, uint32_t np, uint32_t n_ind, const double *maf, const uint8_t *skip,
+                            uint64_t n_sites, double *dose_sum, hipStream_t stream) {
+  if (n_sites == 0) return hipSuccess;
+  const uint64_t wgs = (n_sites + 3) / 4;
+  hipLaunchKernelGGL(site_dose_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, stream, planes, site_stride, np, n_ind, maf,
+                     skip, n_sites, dose_sum);
+  return hipGetLastError();
+}
+
 __global__ void items_kernel(ItemArgs A) {
   const uint32_t s1 = blockIdx.x * blockDim.x + threadIdx.x;
   if (s1 >= A.n_sites) return;
