@@ -355,9 +355,9 @@ __device__ __forceinline__ uint32_t em_pair(const double (&P)[SLOTS][9], uint32_
     // Iteration 0 with its new frequencies given: the three-value form's n0 and the hot loop's bookkeeping, expression for
     // expression.  New frequencies that do not look sane are dropped, and the pair starts at iteration 0 below as it does
     // without them (the per-individual step and, if that one is odd too, its second opinion).
-    // (One case is not the reference's: an individual whose two dens are positive and finite each -- dose_ok -- while their
-    // product, the reference's s, underflows to 0: there every tmp/sum is NaN and nIter 0, here the given step is finite and
-    // counts as iteration 0.  It takes frequencies around 1e-80 handed in through ngsld_set_geno_lkl.)
+    // (An individual whose two dens are positive and finite each while their product, the reference's s, underflows to 0 --
+    // every tmp/sum NaN and nIter 0 there; it takes frequencies around 1e-80 handed in through ngsld_set_geno_lkl -- never
+    // gets here: a site with a den below 2^-500 is not dose_ok, site_dose_kernel in ld_prep.hip.)
     if (have0 && !full) {
       const double n1 = g1, n2 = g2, n3 = g3;
       const double n0 = 1.0 - ((n1 + n2) + n3);

@@ -492,11 +492,14 @@ hipError_t launch_pack_scalars(const double *maf, const double *mean_e, const do
 // the labels the pair kernels give the site (Relabel: a frequency above 1/2 is 1 - m with planes 0 and 2 trading places) -- or
 // -1 where the site is not dose_ok and its pairs keep the per-individual first step:
 //   * the frequency is not strictly inside (0, 1);
-//   * some individual's den = u . a (dose_terms: the kernel's own order of operations) is <= 0 or not finite, or its dosage is
-//     not finite;
+//   * some individual's den = u . a (dose_terms: the kernel's own order of operations) is below kDoseDenMin or not finite, or
+//     its dosage is not finite.  The floor keeps the product of two dens -- the reference's s of that individual at linkage
+//     equilibrium -- a normal double: where the reference's s underflows to 0 (four NaNs, nIter 0) the pair must not be
+//     given a finite first step, and with one site out it is not (tests/test_gpu_first_step_alone.py);
 //   * a triple does not sum to 1 (odd_triple: what signed_rsx looks for, at either label);
 //   * site_skip_kernel marked the site degenerate.
 // One wavefront per site; the sum in a FIXED order: a lane's individuals in slot order, then wave_sum1 over the lanes.
+constexpr double kDoseDenMin = 0x1p-500;  // (the square is 2^-1000: normal)
 __global__ __launch_bounds__(256) void site_dose_kernel(const double *__restrict__ planes, uint64_t site_stride, uint32_t np, uint32_t n_ind,
                                                         const double *__restrict__ maf, const uint8_t *__restrict__ skip, uint64_t n_sites,
                                                         double *__restrict__ dose_sum) {
@@ -515,7 +518,7 @@ __global__ __launch_bounds__(256) void site_dose_kernel(const double *__restrict
       double den, num;
       dose_terms(u, a0, a1, a2, den, num);
       const double d = num / den;
-      ok = ok && den > 0.0 && den < __builtin_inf() && d >= 0.0 && d < __builtin_inf() && !odd_triple(a0, a1, a2);
+      ok = ok && den >= kDoseDenMin && den < __builtin_inf() && d >= 0.0 && d < __builtin_inf() && !odd_triple(a0, a1, a2);
       acc += d;
     }
     const double S = wave_sum1(acc);
