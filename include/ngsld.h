@@ -662,6 +662,64 @@ int ngsld_grid_chromosomes(ngsld_ctx *ctx, uint64_t cap, const char **name, uint
  * entries each, any pointer may be NULL: sum_micro[] and max_micro[] in micro-units, linked[], mean[]. */
 int ngsld_grid_get(ngsld_ctx *ctx, int field, uint64_t cap, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean);
 
+/* ---- Linked pairs on the device (LINKED.md) ---------------------------------------------------------------------------------
+ * The rows of the TSV this context's plan would print that pass a filter, in the table's own order -- without the TSV: the pairs
+ * run again chunk by chunk into device records (every pair kernel, the exact-order replay included), a kernel applies the filter
+ * and measures the surviving rows, two prefix sums place them, and a second kernel stores them compactly: the two sites and the
+ * record(s) of every linked row, and (or) its text, byte for byte the row of the full table.  An emitted pair is a linked row iff
+ * the chosen field is finite and its printed ("%f") value -- |value| with abs_value -- is >= min_weight, both printed maf >=
+ * min_maf, and -- only with a finite max_kb_dist -- dist (as printed) is finite and <= max_kb_dist * 1000.  With the default
+ * INFINITY there is no condition on dist at all: rows across chromosomes and rows without positions pass.  The rule and its
+ * deviations are in LINKED.md.  Both structs start with struct_size, as the pruning structs do. */
+enum {
+  NGSLD_LINKED_RECORDS = 1,   /* s1, s2, std (and ext where the plan has extend_out) */
+  NGSLD_LINKED_TEXT = 2       /* the rows' text */
+};
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_linked_params) */
+  int32_t field;              /* TSV column of the value: 4 r2_ExpG, 5 D, 6 D', 7 r2 (default) */
+  double min_weight;          /* a row needs value >= min_weight (default 0.5; a value equal to it passes; -INFINITY allowed) */
+  double max_kb_dist;         /* finite: a row needs dist <= max_kb_dist * 1000; INFINITY (default): no condition on dist */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  int32_t abs_value;          /* != 0 (default): |value|, as pruning's weight type 'a'; 0: the signed value */
+  int32_t want;               /* NGSLD_LINKED_RECORDS | NGSLD_LINKED_TEXT, at least one */
+} ngsld_linked_params;
+
+/* The linked rows of one chunk of the table's rows, in the table's order.  Pointers are valid only during the callback; the
+ * arrays that were not asked for are NULL (text_len 0). */
+typedef struct {
+  uint64_t n;                 /* linked rows in this batch (> 0) */
+  const uint32_t *s1, *s2;    /* [n] the two sites */
+  const ngsld_rec_std *std;   /* [n] */
+  const ngsld_rec_ext *ext;   /* [n], NULL unless the plan has extend_out */
+  const char *text;           /* the n rows, each as the full table prints it */
+  uint64_t text_len;
+} ngsld_linked_batch;
+
+typedef int (*ngsld_linked_fn)(void *user, const ngsld_linked_batch *b);
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_linked_stats) */
+  uint32_t reserved;          /* 0 */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t rows;              /* linked rows handed to the sink */
+  uint64_t text_bytes;        /* bytes of text handed to the sink */
+  uint64_t host_rows;         /* rows the host formatter wrote (a value beyond the device formatter's range in their chunk) */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, kernel_ms, total_ms;  /* pair kernels + replay, the count + scan + write kernels (kernel time), the whole call */
+  double count_ms, scan_ms, write_ms;    /* kernel_ms by kernel */
+} ngsld_linked_stats;
+
+/* The linked rows after ngsld_plan, streamed: the sink is called once per chunk of the table's rows that has linked rows, in
+ * order, on the calling thread.  A non-zero return of the sink ends the call with that value; the context stays usable.  labels
+ * = n_sites C strings, the TSV's first two columns (NULL: every label prints "(null)"); read only when text is wanted.  The
+ * extended columns are in the text iff the plan has extend_out.  stats may be NULL.  NGSLD_ERR_INVALID for a field outside 4..7,
+ * a NaN min_weight, a max_kb_dist that is NaN or below 0, a min_maf that is NaN, negative or infinite, or want == 0;
+ * NGSLD_ERR_UNSUPPORTED for a finite max_kb_dist with non-integer position gaps. */
+int ngsld_linked_pairs(ngsld_ctx *ctx, const ngsld_linked_params *params, const char *const *labels, ngsld_linked_fn sink,
+                       void *user, ngsld_linked_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

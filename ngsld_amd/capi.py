@@ -99,6 +99,7 @@ SYMBOLS = [
     "ngsld_site_ld", "ngsld_site_ld_get",
     "ngsld_clusters", "ngsld_clusters_sites", "ngsld_clusters_table",
     "ngsld_grid", "ngsld_grid_cells", "ngsld_grid_chromosomes", "ngsld_grid_get",
+    "ngsld_linked_pairs",
 ]
 
 
@@ -192,6 +193,28 @@ class GridStats(C.Structure):
                 ("pairs_ms", C.c_double), ("grid_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class LinkedParams(C.Structure):
+    """ngsld_linked_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("min_weight", C.c_double), ("max_kb_dist", C.c_double),
+                ("min_maf", C.c_double), ("abs_value", C.c_int32), ("want", C.c_int32)]
+
+
+class LinkedBatch(C.Structure):
+    """ngsld_linked_batch (include/ngsld.h)."""
+    _fields_ = [("n", C.c_uint64), ("s1", C.c_void_p), ("s2", C.c_void_p), ("std", C.c_void_p), ("ext", C.c_void_p),
+                ("text", C.c_void_p), ("text_len", C.c_uint64)]
+
+
+class LinkedStats(C.Structure):
+    """ngsld_linked_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("rows", C.c_uint64),
+                ("text_bytes", C.c_uint64), ("host_rows", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("count_ms", C.c_double), ("scan_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
+LINKED_RECORDS, LINKED_TEXT = 1, 2
+LINKED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(LinkedBatch))
 TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 
 
@@ -338,6 +361,8 @@ def lib() -> C.CDLL:
             L.ngsld_grid_cells.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
             L.ngsld_grid_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
             L.ngsld_grid_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
+        if hasattr(L, "ngsld_linked_pairs"):
+            L.ngsld_linked_pairs.argtypes = [vp, C.POINTER(LinkedParams), C.POINTER(C.c_char_p), LINKED_FN, vp, C.POINTER(LinkedStats)]
         _lib = L
     return _lib
 
@@ -1190,6 +1215,50 @@ class Engine:
                                                cells[f"linked_{f}"].ctypes.data, cells[f"mean_{f}"].ctypes.data))
         cells = {k: v[:nc] for k, v in cells.items()}
         return cells, {k: getattr(st, k) for k, _ in GridStats._fields_ if k != "struct_size"}
+
+    def linked_pairs(self, labels: list[str] | None = None, field: int = 7, min_weight: float = 0.5, abs_value: bool = True,
+                     max_kb_dist: float = float("inf"), min_maf: float = 0.0, records: bool = True, text: bool = False,
+                     on_batch=None) -> tuple[dict, dict]:
+        """The linked pairs of the planned table on the device (ngsld_linked_pairs, LINKED.md): (result, stats).  result holds
+        the rows of the TSV that pass the filter, in the table's order, the batches concatenated: with records "s1" and "s2"
+        (uint32), "std" (REC_STD) and, iff the plan has extend_out, "ext" (REC_EXT); with text "text" (bytes: each row as the
+        full table prints it; labels None = "(null)").  on_batch (optional): called with the number of batches so far after
+        each one; a non-zero return ends the call, which then raises NgsldError with that code."""
+        arr = None if labels is None else (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels])
+        want = (LINKED_RECORDS if records else 0) | (LINKED_TEXT if text else 0)
+        p = LinkedParams(C.sizeof(LinkedParams), int(field), float(min_weight), float(max_kb_dist), float(min_maf),
+                         int(bool(abs_value)), want)
+        st = LinkedStats()
+        st.struct_size = C.sizeof(LinkedStats)
+        got = dict(s1=[], s2=[], std=[], ext=[], text=[])
+        calls = [0]
+
+        def sink(_user, bp):
+            b = bp.contents
+            k = int(b.n)
+            if b.s1:
+                got["s1"].append(np.frombuffer(C.string_at(b.s1, k * 4), dtype=np.uint32).copy())
+                got["s2"].append(np.frombuffer(C.string_at(b.s2, k * 4), dtype=np.uint32).copy())
+                got["std"].append(np.frombuffer(C.string_at(b.std, k * REC_STD.itemsize), dtype=REC_STD).copy())
+                if b.ext:
+                    got["ext"].append(np.frombuffer(C.string_at(b.ext, k * REC_EXT.itemsize), dtype=REC_EXT).copy())
+            if b.text:
+                got["text"].append(C.string_at(b.text, b.text_len))
+            calls[0] += 1
+            return int(on_batch(calls[0])) if on_batch is not None else 0
+
+        self._check(self._L.ngsld_linked_pairs(self._h, C.byref(p), arr, LINKED_FN(sink), None, C.byref(st)))
+        cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dtype=dt)  # noqa: E731
+        result = {}
+        if records:
+            result.update(s1=cat(got["s1"], np.uint32), s2=cat(got["s2"], np.uint32), std=cat(got["std"], REC_STD))
+            if self.extend_out:
+                result["ext"] = cat(got["ext"], REC_EXT)
+        if text:
+            result["text"] = b"".join(got["text"])
+        stats = {k: getattr(st, k) for k, _ in LinkedStats._fields_ if k not in ("struct_size", "reserved")}
+        stats["batches"] = calls[0]
+        return result, stats
 
     def blocks(self, labels: list[str], chr: str, start: int, end: int,
                ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:

@@ -25,6 +25,9 @@
 //   * --grid_out FILE --grid_bin_size B (new) and the other --grid_* flags: the LD heat map along each chromosome -- rows, sum,
 //     mean, maximum and linked rows of the site pairs between every two windows of B bp -- binned on the device (ngsld_grid,
 //     GRID.md); taken out of argv the same way, no TSV without --out;
+//   * --linked_out FILE / --linked_outH FILE (new) and the other --linked_* flags: the rows of the table at or above an LD floor,
+//     each as the table prints it and in the table's order, compacted on the device (ngsld_linked_pairs, LINKED.md); taken out
+//     of argv the same way, no TSV without --out; a name ending in .gz is written gzip-compressed;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -163,6 +166,14 @@ struct GridArgs {
   bool is_signed = false;
   ngsld_grid_params p{};
 } grid;
+
+// ---- --linked_* (new): the linked pairs on the device ----
+struct LinkedArgs {
+  bool given = false;  // any --linked_* flag
+  const char *out = nullptr, *outH = nullptr, *field = nullptr, *min_weight = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr;
+  bool is_signed = false;
+  ngsld_linked_params p{};
+} linked;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -401,6 +412,27 @@ void check_grid_args(const Params &pars) {
   one_device(__FUNCTION__, pars, "--grid_out");
 }
 
+void check_linked_args(const Params &pars) {
+  LinkedArgs *la = &linked;
+  if (la->out == nullptr && la->outH == nullptr) error(__FUNCTION__, "the --linked_* options need --linked_out FILE or --linked_outH FILE!");
+  if (la->out != nullptr && la->outH != nullptr) error(__FUNCTION__, "--linked_out and --linked_outH cannot be combined!");
+  if (la->out != nullptr && *la->out == 0) error(__FUNCTION__, "--linked_out needs a file name!");
+  if (la->outH != nullptr && *la->outH == 0) error(__FUNCTION__, "--linked_outH needs a file name!");
+  ngsld_linked_params &p = la->p;
+  p.struct_size = sizeof(p);
+  p.field = 7;
+  p.min_weight = 0.5;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.abs_value = la->is_signed ? 0 : 1;
+  p.want = NGSLD_LINKED_TEXT;
+  column_arg(__FUNCTION__, "--linked_field", la->field, &p.field);
+  number_arg(__FUNCTION__, "--linked_min_weight", la->min_weight, &p.min_weight);
+  dist_arg(__FUNCTION__, "--linked_max_kb_dist", la->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--linked_min_maf", la->min_maf, &p.min_maf);
+  one_device(__FUNCTION__, pars, "--linked_out");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -630,6 +662,48 @@ void run_clusters(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
             (unsigned long)st.largest, (unsigned long)st.edges, (unsigned long)st.pairs);
 }
 
+int write_linked_batch(void *user, const ngsld_linked_batch *b) {
+  return fwrite(b->text, 1, b->text_len, static_cast<FILE *>(user)) == b->text_len ? 0 : 1;
+}
+
+// the rows of the table that pass the filter, as the table prints them; --linked_outH: under the table's header; a name ending
+// in .gz is written gzip-compressed, as --out is
+void run_linked(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  LinkedArgs &la = linked;
+  const char *path = la.out ? la.out : la.outH;
+  std::vector<const char *> lab;
+  if (pos) {
+    lab.resize(pars.n_sites);
+    for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  }
+  const size_t len = std::strlen(path);
+  ngsld_gz *gz = nullptr;
+  FILE *f = nullptr;
+  if (len > 3 && std::strcmp(path + len - 3, ".gz") == 0) {
+    int wfd = -1;
+    if (ngsld_host_gz_open(path, (int)pars.n_threads, &gz, &wfd) != NGSLD_OK) error(__FUNCTION__, "cannot open linked pairs output file!");
+    f = fdopen(wfd, "w");
+  } else {
+    f = fopen(path, "w");
+  }
+  if (f == nullptr) error(__FUNCTION__, "cannot open linked pairs output file!");
+  if (la.outH) {
+    char hdr[512];
+    const size_t hn = ngsld_host_format_header(hdr, sizeof(hdr), pars.extend_out);
+    if (fwrite(hdr, 1, hn, f) != hn) error(__FUNCTION__, "cannot write linked pairs output file!");
+  }
+  ngsld_linked_stats st{};
+  st.struct_size = sizeof(st);
+  const int rc = ngsld_linked_pairs(ctx, &la.p, pos ? lab.data() : nullptr, write_linked_batch, f, &st);
+  if (rc > 0) error(__FUNCTION__, "cannot write linked pairs output file!");  // (the sink's own return value: the library's are negative)
+  if (rc != NGSLD_OK) error("ngsld_linked_pairs", ngsld_last_error(ctx));
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write linked pairs output file!");
+  if (gz != nullptr && ngsld_host_gz_close(gz) != NGSLD_OK) error(__FUNCTION__, "cannot write linked pairs output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> Linked pairs: %lu of %lu pairs (%lu bytes, %lu rows formatted on the host)\n", (unsigned long)st.rows,
+            (unsigned long)st.pairs, (unsigned long)st.text_bytes, (unsigned long)st.host_rows);
+}
+
 int write_blocks_text(void *user, const char *text, uint64_t len) {
   return fwrite(text, 1, len, static_cast<FILE *>(user)) == len ? 0 : 1;
 }
@@ -745,6 +819,10 @@ const Family kFamilies[] = {
      {{"grid_out", &grid.out}, {"grid_bin_size", &grid.bin_size}, {"grid_ld", &grid.ld}, {"grid_max_kb_dist", &grid.max_kb_dist},
       {"grid_min_maf", &grid.min_maf}, {"grid_linked_min", &grid.linked_min}},
      "grid_signed", &grid.is_signed, &grid.given, check_grid_args, run_grid, "LD grid"},  // (a pass of its own)
+    {"linked_",
+     {{"linked_out", &linked.out}, {"linked_outH", &linked.outH}, {"linked_field", &linked.field},
+      {"linked_min_weight", &linked.min_weight}, {"linked_max_kb_dist", &linked.max_kb_dist}, {"linked_min_maf", &linked.min_maf}},
+     "linked_signed", &linked.is_signed, &linked.given, check_linked_args, run_linked, "linked pairs"},  // (a pass of its own)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1211,7 +1289,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
@@ -1342,7 +1420,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given && !grid.given &&  // (the clusters and the grid need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given && !linked.given &&  // (the clusters, the grid and the linked pairs need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the

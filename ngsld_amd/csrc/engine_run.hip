@@ -1072,7 +1072,7 @@ int SiteFilter::upload(ngsld_ctx *c) {
   return NGSLD_OK;
 }
 
-int RecordPass::open(ngsld_ctx *ctx, uint64_t chunk, const uint8_t *only_rows, bool fit_longest_row) {
+int RecordPass::open(ngsld_ctx *ctx, uint64_t chunk, const uint8_t *only_rows, bool fit_longest_row, bool with_ext) {
   c = ctx;
   chunk_pairs = chunk;
   rows = only_rows;
@@ -1087,6 +1087,7 @@ int RecordPass::open(ngsld_ctx *ctx, uint64_t chunk, const uint8_t *only_rows, b
     cap = std::max<uint64_t>(std::min<uint64_t>(pairs, chunk), longest);
   }
   HIP_TRY(c, d_rec.resize(cap));
+  if (with_ext) HIP_TRY(c, d_ext.resize(cap));
   HIP_TRY(c, ev.create());
   return NGSLD_OK;
 }
@@ -1112,7 +1113,7 @@ int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const
     if (ch.pairs > d_rec.n) return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(ch.pairs) + " pairs does not fit the record buffer");
     if (ch.pairs > 0) {
       const auto t0 = std::chrono::steady_clock::now();
-      int rc = ngsld_run_device(c, r0, r1, d_rec.p, nullptr, nullptr);  // (the ctx's stream: records final, replay done)
+      int rc = ngsld_run_device(c, r0, r1, d_rec.p, d_ext.p, nullptr);  // (the ctx's stream: records final, replay done)
       if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
       if (rc != NGSLD_OK) return rc;
       if (pairs_ms) *pairs_ms += ms_since(t0);
@@ -1121,9 +1122,7 @@ int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const
         if (rc != NGSLD_OK) return rc;
       }
       const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-      uint64_t max_items = (1ull << 22) * 4;  // (a launch's grid stays below 2^32 threads)
-      if (const char *e = test_knob("RECORD_SLICE_ITEMS"))  // tests: a chunk's items in many launches
-        max_items = std::min<uint64_t>(max_items, std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)));
+      const uint64_t max_items = record_slice_items();
       HIP_TRY(c, hipEventRecord(ev.a, c->stream));
       for (uint64_t off = i0; off < i1; off += max_items) {
         launch(ch, c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));

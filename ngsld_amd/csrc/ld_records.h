@@ -1,7 +1,7 @@
 // ld_records.h -- the consumer side of the pair records on the device: which record a lane of a work item reads, a TSV
 // column's field of a record, a wavefront's max and sum, the words of the sum / max / linked accumulators.  Shared by the TSV rows (ld_text.hip) and the record passes of ngsld_prune,
-// ngsld_decay, ngsld_blocks, ngsld_site_ld, ngsld_clusters and ngsld_grid (prune.hip, decay.hip, blocks.hip, site_ld.hip, cluster.hip,
-// grid.hip), which all map one wavefront to an item and one lane to a candidate.  Not part of the ld_device.h umbrella: the pair kernels never see it.
+// ngsld_decay, ngsld_blocks, ngsld_site_ld, ngsld_clusters, ngsld_grid and ngsld_linked_pairs (prune.hip, decay.hip, blocks.hip,
+// site_ld.hip, cluster.hip, grid.hip, linked.hip), which all map one wavefront to an item and one lane to a candidate.  Not part of the ld_device.h umbrella: the pair kernels never see it.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // record_pass.h -- the host frame of the record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks
-// (blocks.hip), ngsld_site_ld (site_ld.hip), ngsld_clusters (cluster.hip) and ngsld_grid (grid.hip) read the records of rows chunk
+// (blocks.hip), ngsld_site_ld (site_ld.hip), ngsld_clusters (cluster.hip), ngsld_grid (grid.hip) and ngsld_linked_pairs (linked.hip) read the records of rows chunk
 // by chunk and run a kernel of their own over each chunk's items (ld_records.h).  What they share on the host is here, once: the
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
 // linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ.
@@ -38,6 +38,14 @@ constexpr uint64_t kRecordChunkPairs = 1ull << 24;
 // the chunk of a pass: kRecordChunkPairs, or a test knob's smaller value (knob: test_knob("NAME") or null)
 inline uint64_t record_chunk(const char *knob) {
   return knob ? std::max<uint64_t>(1, std::min<uint64_t>(kRecordChunkPairs, std::strtoull(knob, nullptr, 10))) : kRecordChunkPairs;
+}
+
+// the items of one launch of a pass's kernel: a launch's grid stays below 2^32 threads at one wavefront per item (2^24 items), or
+// NGSLD_TEST_RECORD_SLICE_ITEMS if that is fewer (tests: a chunk's items in many launches)
+inline uint64_t record_slice_items() {
+  uint64_t max_items = (1ull << 22) * 4;
+  if (const char *e = test_knob("RECORD_SLICE_ITEMS")) max_items = std::min<uint64_t>(max_items, std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)));
+  return max_items;
 }
 
 // two events that bracket device work on the context's stream; add_elapsed: *ms += their span once the second has passed
@@ -79,8 +87,9 @@ struct RecordPass {
   // The record buffer and the events.  The rows: every row, or the rows s with rows[s] != 0 (it must outlive run).  Chunks of
   // consecutive rows of up to chunk_pairs records; a row is never cut, so the buffer holds the chunk (at most the rows' pairs)
   // or the longest row where that is longer -- or, with fit_longest_row false, just chunk_pairs records: a longer row is refused
-  // in run ("a row of N pairs does not fit the record buffer").
-  int open(ngsld_ctx *c, uint64_t chunk_pairs, const uint8_t *rows = nullptr, bool fit_longest_row = true);
+  // in run ("a row of N pairs does not fit the record buffer").  with_ext: a second buffer of as many 40 B records, which the pair
+  // kernels fill as the plan's extend_out has them (ngsld_linked_pairs prints them).
+  int open(ngsld_ctx *c, uint64_t chunk_pairs, const uint8_t *rows = nullptr, bool fit_longest_row = true, bool with_ext = false);
   // Every chunk: ngsld_run_device + ngsld_finish_device on the context's stream, so every record is final (replayed pairs carry
   // their replayed values); before; launch for each slice of the chunk's items, every slice below 2^32 threads at one wavefront
   // per item (2^24 items, or NGSLD_TEST_RECORD_SLICE_ITEMS if that is fewer), all of them between two events; the wait for the
@@ -88,13 +97,18 @@ struct RecordPass {
   // counts the chunks.
   int run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const Step &before, const Launch &launch, const Step &after = nullptr);
   ngsld_rec_std *records() const { return d_rec.p; }
-  void close() { d_rec.release(); }
+  ngsld_rec_ext *ext_records() const { return d_ext.p; }  // null unless opened with_ext
+  void close() {
+    d_rec.release();
+    d_ext.release();
+  }
 
  private:
   ngsld_ctx *c = nullptr;
   uint64_t chunk_pairs = 0;
   const uint8_t *rows = nullptr;
   DevBuf<ngsld_rec_std> d_rec;
+  DevBuf<ngsld_rec_ext> d_ext;
   EventPair ev;
 };
 
