@@ -269,8 +269,17 @@ struct ngsld_ctx {
   bool have_geno = false;
   DevBuf<double> d_planes, d_maf, d_mean, d_rsx, d_sc4;
   // [n_sites] sums of the sites' posterior dosages (ld_prep.hip, site_dose_kernel): there only where the run kernel takes each
-  // pair's first EM step from them -- every individual counting, two to eight slots (NGSLD_TEST_FIRST_STEP=0: nowhere)
+  // pair's first EM step from them -- every individual counting, two to eight slots (NGSLD_TEST_FIRST_STEP=0: the sums are there, for dose_ok alone)
   DevBuf<double> d_dose_sum;
+  bool first_step_on = true;  // (NGSLD_TEST_FIRST_STEP=0, read when a matrix is set: the sums are still there, for dose_ok)
+  // {sum e1 e2, sum d1 d2} of a launch's pairs, written by pair_ld_moments_kernel in front of the run kernel (engine_run.hip,
+  // timed_launch): one array per stream that carries such launches (launches on different streams may be in flight together),
+  // grown on demand
+  static constexpr int kMomentStreams = 4;
+  DevBuf<double> d_moments[kMomentStreams];
+  hipStream_t moments_stream[kMomentStreams] = {nullptr, nullptr, nullptr, nullptr};  // (compared only, never used: a caller's may be gone)
+  hipEvent_t moments_done[kMomentStreams] = {nullptr, nullptr, nullptr, nullptr};     // behind the last launch that read the array
+  int moments_used = 0;
   DevBuf<int> d_status;
   std::vector<double> h_maf, h_pos_dist;
   // hard-called matrices (kHard): per-site genotype bit sets

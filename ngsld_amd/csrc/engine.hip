@@ -185,7 +185,8 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
   }
   HIP_TRY(c, launch_pack_scalars(c->d_maf.p, c->d_mean.p, c->d_rsx.p, c->d_skip.p, c->d_sc4.p, n_sites, c->stream));
   // the run kernel's first EM step from dosages (ld_kernel_run.h): the per-site sums and flags, from the frequencies just packed
-  if (cfg.kernel == kRun && !ignore_miss && cfg.slots >= 2 && cfg.slots <= 8 && !test_knob_is("FIRST_STEP", "0")) {
+  if (cfg.kernel == kRun && !ignore_miss && cfg.slots >= 2 && cfg.slots <= 8) {
+    c->first_step_on = !test_knob_is("FIRST_STEP", "0");
     HIP_TRY(c, c->d_dose_sum.resize(n_sites));
     HIP_TRY(c, launch_site_dose(c->d_planes.p, 3ull * c->np, c->np, (uint32_t)n_ind, c->d_maf.p, c->d_skip.p, n_sites, c->d_dose_sum.p,
                                 c->stream));
@@ -316,6 +317,9 @@ void ngsld_destroy(ngsld_ctx *c) {
   (void)hipDeviceSynchronize();
   if (c->exact_stream) (void)hipStreamDestroy(c->exact_stream);
   c->d_planes.release(); c->d_maf.release(); c->d_mean.release(); c->d_rsx.release(); c->d_sc4.release(); c->d_dose_sum.release(); c->d_runs.release(); c->d_skip.release(); c->d_skip_count.release();
+  for (auto &b : c->d_moments) b.release();
+  for (auto &e : c->moments_done)
+    if (e) (void)hipEventDestroy(e);
   c->d_hard_masks.release(); c->d_hard_u.release(); c->d_all_hard.release();
   c->d_xplanes.release(); c->d_xmaf.release(); c->d_xT.release(); c->d_xdepth.release(); c->d_xperm.release(); c->h_xstage[0].release(); c->h_xstage[1].release();
   c->lane_scratch_dev.release();

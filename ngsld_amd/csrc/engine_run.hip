@@ -9,6 +9,93 @@
 namespace ngsld {
 namespace eng {
 
+// The run kernel with every individual counting takes each pair's Pearson cross moment and first-step dosage sum from an
+// array that pair_ld_moments_kernel (ld_pair_moments.hip) fills right in front of it, on the same stream: 16 bytes a pair.
+// Where the array for all of the launch's pairs has no room (room_for; tests: NGSLD_TEST_MOMENTS_PAIRS) the launch's rows are
+// cut into several grids, each behind its own pass -- the records are the same bits, a pair's sums do not depend on the cut.
+// The array is as large as the launch (configs[2] in one launch: 98.7 M pairs, 1.58 GB), one per stream that carries such
+// launches, at most four; each keeps what it grew to.  Its first 2^22 pairs (64 MB; 256 MB for four streams) are taken whatever
+// room_for answers, like a context's other fixed buffers, so under ngsld_set_memory_budget up to that much lies outside the cap.
+// NGSLD_TEST_PAIR_MOMENTS=0: no pass, the kernel forms both sums per pair as it did before the pass existed (A/B, tests).
+static hipError_t launch_run_with_moments(ngsld_ctx *c, const PairArgs &a, hipStream_t stream) {
+  const std::vector<uint64_t> &ro = c->h_row_off;
+  const uint64_t total = ro[a.row1] - ro[a.row0];
+  if (total == 0) return hipSuccess;
+  uint64_t longest = 0;
+  for (uint64_t r = a.row0; r < a.row1; ++r) longest = std::max(longest, ro[r + 1] - ro[r]);
+  int k = 0;
+  while (k < c->moments_used && c->moments_stream[k] != stream) ++k;
+  if (k == c->moments_used) {
+    if (k == ngsld_ctx::kMomentStreams) {  // (more streams than arrays: the last one changes hands once its work is done --
+      k = ngsld_ctx::kMomentStreams - 1;   // by the event behind it: the stream itself may be a caller's, destroyed since)
+      const hipError_t e = hipEventSynchronize(c->moments_done[k]);
+      if (e != hipSuccess) return e;
+    } else {
+      ++c->moments_used;
+      const hipError_t e = hipEventCreateWithFlags(&c->moments_done[k], hipEventDisableTiming);
+      if (e != hipSuccess) {
+        --c->moments_used;
+        return e;
+      }
+    }
+    c->moments_stream[k] = stream;
+  }
+  DevBuf<double> &buf = c->d_moments[k];
+  uint64_t want = total;
+  if (const char *e = test_knob("MOMENTS_PAIRS")) want = std::min<uint64_t>(want, std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)));
+  want = std::max(want, longest);  // (a row is never cut)
+  uint64_t cap = buf.n / 2;
+  if (cap < want) {
+    // (2^22 pairs, 64 MB, are had whatever room_for says, like a context's other fixed buffers: under a memory budget the text
+    // groups are that size, and a launch cut row by row is a hundred thousand launches)
+    const uint64_t floor = std::max(std::max(longest, cap), std::min<uint64_t>(want, 1ull << 22));
+    uint64_t grow = want;
+    while (grow > floor && !room_for(grow * 16, 2ull << 30, 256ull << 20)) grow = std::max(floor, grow / 2);
+    if (grow > cap) {
+      const hipError_t e = buf.resize(2 * grow);
+      if (e != hipSuccess) return e;
+      cap = grow;
+    }
+  }
+  cap = std::min(cap, want);
+  const bool masked = false;
+  for (uint64_t r0 = a.row0; r0 < a.row1;) {
+    uint64_t r1 = r0 + 1;
+    while (r1 < a.row1 && ro[r1 + 1] - ro[r0] <= cap) ++r1;
+    if (ro[r1] > ro[r0]) {
+      MomentArgs m{};
+      m.planes = a.planes;
+      m.site_stride = a.site_stride;
+      m.np = a.np;
+      m.n_ind = a.n_ind;
+      m.maf = a.maf;
+      m.n_sites = c->n_sites;
+      m.items_all = a.items_all;
+      m.item_off = a.item_off;
+      m.row_end = c->d_row_end.p;
+      m.row0 = (uint32_t)r0;
+      m.row1 = (uint32_t)r1;
+      m.dose = (a.dose_sum != nullptr && c->cfg.slots >= 2 && c->cfg.slots <= 8) ? 1 : 0;
+      m.rec0 = ro[r0];
+      m.out = buf.p;
+      hipError_t e = launch_pair_moments(m, c->h_row_end.data(), stream);
+      if (e != hipSuccess) return e;
+      PairArgs b = a;
+      b.row0 = (uint32_t)r0;
+      b.row1 = (uint32_t)r1;
+      b.items = c->d_items.p + c->h_item_off[r0];
+      b.n_items = c->h_item_off[r1] - c->h_item_off[r0];
+      b.runs = c->d_runs.p + c->h_run_off[r0];
+      b.n_runs = c->h_run_off[r1] - c->h_run_off[r0];
+      b.moments = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(buf.p) - 16 * (ro[r0] - a.out_base));
+      e = launch_pair_kernel(c->cfg, masked, b, stream);
+      if (e != hipSuccess) return e;
+    }
+    r0 = r1;
+  }
+  return hipEventRecord(c->moments_done[k], stream);
+}
+
 hipError_t timed_launch(ngsld_ctx *c, const PairArgs &a, hipStream_t stream) {
   if (c->ev_used == c->ev_pool.size()) {
     hipEvent_t b, e;
@@ -21,7 +108,10 @@ hipError_t timed_launch(ngsld_ctx *c, const PairArgs &a, hipStream_t stream) {
   auto &ev = c->ev_pool[c->ev_used++];
   hipError_t r = hipEventRecord(ev.first, stream);
   if (r != hipSuccess) return r;
-  r = launch_pair_kernel(c->cfg, c->params.ignore_miss_data != 0, a, stream);
+  if (c->cfg.kernel == kRun && c->params.ignore_miss_data == 0 && a.row1 > a.row0 && !test_knob_is("PAIR_MOMENTS", "0"))
+    r = launch_run_with_moments(c, a, stream);
+  else
+    r = launch_pair_kernel(c->cfg, c->params.ignore_miss_data != 0, a, stream);
   if (r != hipSuccess) return r;
   return hipEventRecord(ev.second, stream);
 }
@@ -61,7 +151,8 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
   a.row1 = (uint32_t)r1;
   a.planes_bytes = c->n_sites * 3ull * c->np * sizeof(double);
   a.sc4 = c->d_sc4.p;
-  a.dose_sum = c->cfg.kernel == kRun ? c->d_dose_sum.p : nullptr;
+  a.dose_ok = c->cfg.kernel == kRun ? c->d_dose_sum.p : nullptr;
+  a.dose_sum = c->first_step_on ? a.dose_ok : nullptr;
   a.out_base = c->h_row_off[r0];
   a.out_std = d_std;
   a.out_ext = d_ext;

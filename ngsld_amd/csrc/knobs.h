@@ -18,7 +18,7 @@
 //   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS, GRID_LDS_BYTES, GRID_CHUNK_PAIRS,
 //   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST,
 //   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT,
-//   FIRST_STEP
+//   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS
 // LINKED_FORCE_HOST=1: every chunk of ngsld_linked_pairs takes the host formatter, as BLOCKS_HOST_ROWS does for the block matrices.
 // PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS and SUM_WRAP_LIMIT bring the large-job paths of the record passes (record_pass.h) down to jobs of a few thousand pairs, where
 // tests/test_gpu_record_pass_large.py holds them to the passes' rules: ngsld_prune's chunk loop (its edge arrays regrown and its
@@ -26,6 +26,10 @@
 // (2^24 items otherwise), and the guard of the integer sums (max |q| tracked from 2^25 rows on, refused from 2^63 on).
 // FIRST_STEP=0: the run kernel takes no pair's first EM step from the sites' dosages (ld_kernel_run.h) -- every pair starts at
 // iteration 0 with the per-individual step, and the records are what they were before that step existed (A/B, tests).
+// PAIR_MOMENTS=0: no pair_ld_moments_kernel in front of the run kernel (engine_run.hip, timed_launch) -- the kernel forms each pair's
+// Pearson cross moment and first-step dosage sum itself, and the records are what they were before the pass existed (A/B, tests;
+// one exception, a site whose lane product of dens underflows: site_dose_kernel, ld_prep.hip).
+// MOMENTS_PAIRS=n: the pass's array holds at most n pairs (never less than a row's), so a launch's rows are cut into several grids.
 // (The knobs of closed A/B experiments -- lane caps and waves, sort-key tilings, run lengths, tile rows, text batch sizes -- are
 // gone; their measurements are in HISTORY.md.)
 #pragma once

@@ -14,7 +14,7 @@
 // its four `tmp/sum` accumulations (gen_func.cpp:1098-1104) are linear in R[G] = sum_i P_i[G]/s_i:
 //   ff_k/(2x) = f_k * sum_h f_h * R[G(k,h)] / x.
 // Per individual and iteration that is 9 FMA (s) + one refined reciprocal + 9 FMA (R) instead of the
-// reference's ~168 flops; f64 throughout, no MFMA (nothing is shared across pairs to contract over).
+// reference's ~168 flops; f64 throughout, no MFMA in the EM (nothing there is shared across pairs to contract over).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -148,6 +148,13 @@ struct PairArgs {
   // [n_sites] the sum of a site's dosages under its own labels (site_dose_kernel, ld_prep.hip); negative: the site takes no
   // part (not dose_ok).  Null: every pair starts at iteration 0 with the per-individual step.
   const double *dose_sum;
+  // the same array where it exists, also with the first step switched off (NGSLD_TEST_FIRST_STEP=0): which sites are dose_ok (run kernel)
+  const double *dose_ok;
+  // run kernel, every individual counting: {sum e1 e2, sum d1 d2} of the launch's pairs under the kernel's labels, from
+  // pair_ld_moments_kernel (ld_pair_moments.hip), record `rec` of the output buffers at moments[2 * rec] (the engine hands
+  // over the array's address less the launch's first record).  Null (NGSLD_TEST_PAIR_MOMENTS=0): both sums are formed per
+  // pair inside the kernel.
+  const double *moments;
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -59,6 +59,23 @@ hipError_t launch_pair_bres(int slots, bool masked, const PairArgs &args, hipStr
 // cleared when any triple is neither a called genotype (1,0,0) / (0,1,0) / (0,0,1) nor three equal values
 hipError_t launch_classify_hard(const double *planes, uint64_t site_stride, uint32_t np, uint32_t n_ind, uint64_t n_sites,
                                 uint64_t *masks, double *u, int *all_hard, hipStream_t stream);
+// pair_ld_moments_kernel (ld_pair_moments.hip), in front of every launch of the run kernel with every individual counting:
+// rows [row0, row1) of the plan, out[record - rec0] = {sum e1 e2, sum d1 d2} of each kept pair (dose == 0: the first sum alone)
+struct MomentArgs {
+  const double *planes;
+  uint64_t site_stride;
+  uint32_t np, n_ind;
+  const double *maf;
+  uint64_t n_sites;
+  const Item *items_all;
+  const uint64_t *item_off;  // [n_sites + 1]
+  const uint32_t *row_end;   // [n_sites] one past each row's last candidate
+  uint32_t row0, row1;
+  uint32_t dose;
+  uint64_t rec0;             // the plan's record index of the launch's first pair
+  double *out;               // [pairs of the launch][2]
+};
+hipError_t launch_pair_moments(const MomentArgs &args, const uint32_t *h_row_end, hipStream_t stream);
 // candidate s2 sites per work item
 inline uint32_t item_span(const PairConfig &cfg, uint32_t pairs_per_item) {
   if (uses_runs(cfg.kernel)) return 64u;  // run form: candidates are addressed as 64 * item + offset

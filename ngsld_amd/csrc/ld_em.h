@@ -526,7 +526,8 @@ __device__ __forceinline__ void write_pair(const PairArgs &A, uint64_t slot, dou
     const double q1 = fabs(hm1) <= fabs(1 - hm1) ? fabs(hm1) : fabs(1 - hm1);
     // (NaN frequencies fail both comparisons)
     // host_only: reasons that concern r2_ExpG -- what the device-side replay of called genotypes (ld_replay.hip) leaves alone
-    const bool pearson_bad = !constant_site && (double)A.n_ind * a1 * a2 > kPearsonCond;  // (a constant site: NaN on every path)
+    const double cond = (double)A.n_ind * a1 * a2;
+    const bool pearson_bad = !constant_site && cond > kPearsonCond;  // (a constant site: NaN on every path)
     bool host_only = odd_site || (pearson_bad && !A.pearson_on_device);
     // (written so that a NaN anywhere -- frequencies, D', r2 -- flags the pair)
     const double amp_q = 1.0 / q0 + 1.0 / q1, big = fabs(Dp) >= o.r2 ? fabs(Dp) : o.r2;
@@ -536,12 +537,21 @@ __device__ __forceinline__ void write_pair(const PairArgs &A, uint64_t slot, dou
     // rounding noise of zero a different sign ("-0.000000"): those pairs are replayed too, so that the text is the
     // reference's byte for byte.  Error bounds: hap, hap_maf and D are absolute (a few ulp of 1); D' and r2 divide by
     // products of the margins q (relative error ~ulp / q); r2_ExpG carries ~ulp * n * rsx1 * rsx2 of cancellation.
+    // Its margin is sized with the roundings a term of sum e1 e2 passes on its way into the sum, times the sum's bound 4 n:
+    // 4 n stands for the in-kernel order (the lane's slots, then six DPP levels: 17 at eight slots, 19 at ten), 12 n for the
+    // order of pair_ld_moments_kernel (16 + np / 16 roundings: 48 at np = 512, 56 at 640 -- three times as many).
     // (flag_text: only where the records may become text -- ngsld_run; ngsld_run_device leaves them on the device)
     constexpr double kUlp = 0x1p-52;
     const double d_abs = A.flag_text ? 32 * kUlp : -1.0;  // (negative: near_rounding is never true)
     const double amp = A.flag_text ? amp_q : 0.0;
     // (a pair whose moment is ill conditioned: this r2_ExpG is not the number to look at -- whoever replays the pair does)
-    host_only = host_only || (!pearson_bad && near_rounding(o.r2_ExpG, 0.5 * d_abs * (1.0 + 4.0 * (double)A.n_ind * a1 * a2)));
+    // (0.5 d_abs (1 + 4 n a1 a2) resp. 12 n a1 a2, written with the products the lines above already hold: in the run kernel
+    // at eight slots the earlier form's loop-invariant 4 n a1 and 0.5 d_abs were hoisted over the pair loop and were the two
+    // VGPR pairs that spilled.  With the 4 it is the earlier form's very double: the two differ by factors of two only, which
+    // commute with every rounding -- n a1 a2 against 4 n a1 a2, fma(2, c, 0.5) against (1 + 4 c) / 2, d_abs against d_abs / 2
+    // -- so every kernel family flags the pairs it flagged)
+    const double half_kn = A.moments != nullptr ? 6.0 : 2.0;
+    host_only = host_only || (!pearson_bad && near_rounding(o.r2_ExpG, d_abs * fma(half_kn, cond, 0.5)));
     flag = flag || host_only || fabs(D) < 2 * d_abs || near_rounding(D, d_abs) ||
            near_rounding(Dp, 2 * d_abs * (1.0 + fabs(Dp) * amp)) || near_rounding(o.r2, 2 * d_abs * (1.0 + o.r2 * amp));
     if (A.out_ext != nullptr)

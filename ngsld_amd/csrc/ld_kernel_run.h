@@ -18,31 +18,35 @@ namespace ngsld {
 // With the posterior dosage d = alpha_1 + 2 alpha_2 the expected count of haplotype (1,1) is d1 d2 / 2, so iteration 0 is
 //   f3' = S12 / (4n),  f2' = S1 / (2n) - f3',  f1' = S2 / (2n) - f3',  f0' = 1 - ((f1' + f2') + f3'),   S12 = sum d1 d2, S = sum d.
 // S is a per-site scalar, summed once per matrix by site_dose_kernel (ld_prep.hip), which also says whether the site may
-// take part (dose_ok).  The row's dosages are formed once per run, from its planes in LDS, and stay in LDS (4 KB at eight
-// slots).  The candidate's are formed from its planes right before stage_pair turns them into P: den and num per slot, ONE
-// reciprocal per lane for all its slots (RcpTree), one FMA per slot into S12 -- 6 instructions per slot and the tree,
-// against the step's 17 and its tree, contraction and three-value reduction.  (A dose array beside the planes, each
-// candidate's 4 KB brought in with its site copy, was built first and has no place to land: four more 4 KB buffers make
-// 88 KB of LDS where 80 KB let two workgroups share a CU, and the kernel has not one VGPR to spare -- with eight doubles per
-// lane held a pair ahead the cross-compile spilled 28, and any product hoisted out of the pair loop spills as well: see
-// the note at g1 .. g3.)
-// S12 has a REDUCTION OF ITS OWN, a second wave_sum1_bcast in front of stage_pair: six DPP adds and a readlane more per pair
-// than one pass for both sums would take.  The lane's share of S12 is complete before P exists, that of the Pearson moment
-// only after it; carried across stage_pair as a VGPR pair and reduced beside the moment (the same DPP steps, interleaved),
-// the cross-compile spills 2 VGPRs to scratch at eight slots.  The total is wavefront-uniform and crosses in SGPRs.  The
-// moment's own reduction -- and with it r2_ExpG -- is what it was.
+// take part (dose_ok).  S12 -- and the Pearson cross moment sum e1 e2, e = a1 + 2 a2 -- are sums over the individuals of
+// products of two PER-SITE vectors (each site's labels depend on its own frequency only: Relabel): over a launch they are the
+// band of X X^T, the one contraction of the workload that IS shared across pairs.  pair_ld_moments_kernel
+// (ld_pair_moments.hip) forms them on the f64 matrix pipe in front of every launch, 16 bytes a pair (PairArgs::moments,
+// mom_on; every individual counting, any slot count); they come in with the candidate's site copy (lane 2's 16 bytes beside
+// its scalars) and are read behind stage_pair: no dosage, no reciprocal tree, no wavefront reduction in front of the EM.
+// The centring fma(-n mean1, mean2, sum e1 e2), have0 / dose_ok / skip and em_pair's FIRST bookkeeping are what they were.
+//
+// A pair with a site that is not dose_ok by itself keeps the in-kernel moment: its records do not depend on the pass.
+// PairArgs::moments == nullptr (NGSLD_TEST_PAIR_MOMENTS=0: tests, A/B) is the kernel as it was before that pass, the same
+// records bit for bit (but for a row whose lane product of dens underflows, which site_dose_kernel now keeps out of the
+// step as it kept such a candidate: ld_prep.hip): the row's dosages are formed once per run, from its planes in LDS, and stay in LDS (4 KB at eight
+// slots); the candidate's are formed from its planes right before stage_pair turns them into P -- den and num per slot, ONE
+// reciprocal per lane for all its slots (RcpTree), one FMA per slot into S12, a wave_sum1_bcast of its own (the lane's share
+// of S12 is complete before P exists, that of the moment only after it; carried across stage_pair the cross-compile spills) --
+// and the moment is read off P and reduced behind stage_pair.  (Both paths live in ONE kernel, chosen by a wavefront-uniform
+// argument like first_on: the row's 4 KB of LDS stay allocated.  HISTORY.md has what else was tried for the in-kernel form.)
 // The candidate's S comes through the scalar cache, behind stage_pair (see there).  Everything is formed under the
 // kernel's labels (Relabel), so no sum needs turning round.  A pair with a site that is not dose_ok, or whose given
 // frequencies fail em_pair's sanity test (a product of dens that underflowed: NaN), starts at iteration 0 as before; the
-// choice is wavefront-uniform, and under a row that is not dose_ok no candidate forms its dosages.  Nine and ten slots have no LDS left
-// for the row's dosages and spill already: they keep the per-individual first step.  The SKIP variant takes the step like
+// choice is wavefront-uniform.  Nine and ten slots spill already: they keep the per-individual first step (and take the
+// moment from the pass).  The SKIP variant takes the step like
 // the plain one: which of the two a launch gets depends on the context (marks on or off, a replay that can take the marked
 // pairs), and the pairs both compute must come out the same bits in both (tests/test_gpu_replay_lkl.py,
 // tests/test_gpu_multi_native.py).
 template <int SLOTS, bool MASKED, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   constexpr int kSiteBytes = SLOTS * 64 * 3 * 8;
-  constexpr int kBuf = kSiteBytes + 32;
+  constexpr int kBuf = kSiteBytes + 48;  // a site's planes, its four scalars, the pair's two sums (mom_on)
   constexpr uint32_t kNp = SLOTS * 64;
   // (ten slots: five site buffers of 15 KB leave 5 KB for rings and list under the 80 KB that let two workgroups share a CU)
   constexpr uint32_t kRing = SLOTS <= 9 ? 32 : 8;
@@ -61,7 +65,8 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   const Run run = A.runs[blockIdx.x];
   const Item *g_items = A.items_all + run.first_item;
   const uint32_t s1 = g_items[0].s1;
-  const double m1 = A.sc4[4 * (uint64_t)s1], mean1 = A.sc4[4 * (uint64_t)s1 + 1], rsx1 = A.sc4[4 * (uint64_t)s1 + 2];
+  const double m1 = A.sc4[4 * (uint64_t)s1], mean1 = A.sc4[4 * (uint64_t)s1 + 1];
+  const double rsx1 = uniform(A.sc4[4 * (uint64_t)s1 + 2]);  // (only the flushes read it: in SGPRs, or their spill lanes, it holds no VGPR through the pairs)
   const bool skip1 = SKIP && A.sc4[4 * (uint64_t)s1 + 3] != 0.0;
   char *lds_a = smem;
   char *lds_b = smem + kSiteBytes + wave * kBuf;
@@ -74,10 +79,14 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   const uint32_t s2_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)L->items[0].s2_begin);
   const uint64_t rec_base = g_items[0].first_record - A.out_base;
   const bool first_on = kFirst && A.dose_sum != nullptr;  // (a kernel argument: wavefront-uniform)
+  const bool mom_on = !MASKED && A.moments != nullptr;    // (likewise) both sums come from pair_ld_moments_kernel
+  const bool has_ok = kFirst && A.dose_ok != nullptr;      // (likewise) the sites' dosage sums are there, if only for their signs
   double S1 = -1.0;
-  if (first_on) {
-    S1 = uniform(A.dose_sum[s1]);
+  if (has_ok) {
+    S1 = uniform(A.dose_ok[s1]);
     S1 = uniform(S1 < 0.0 ? S1 : 0.5 * S1);  // half the sum is what the pairs use (in SGPRs)
+  }
+  if (first_on && !mom_on) {  // the row's dosages, for the sums formed per pair
     const bool flip1 = m1 > 0.5;  // (Relabel: the row's labels are the same for all its pairs)
     const DoseWeights u = dose_weights(flip1 ? 1.0 - m1 : m1);
     const double *pa = reinterpret_cast<const double *>(lds_a);
@@ -104,11 +113,15 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)L->cand[j]);
     return Cand{s2_base + off, rec_base + j, true};
   };
-  auto dma_site = [&](uint32_t s2) {
-    dma_site_to_lds<SLOTS>(A.planes + (uint64_t)s2 * A.site_stride, lds_b, lane, 0, 1);
-    if (lane < 2)
-      __builtin_amdgcn_global_load_lds((glb_void_t *)(reinterpret_cast<const char *>(A.sc4 + 4 * (uint64_t)s2) + lane * 16),
-                                       (lds_void_t *)(lds_b + kSiteBytes), 16, 0, 0);
+  // (mom_on: the pair's two sums travel with the site like its scalars -- lane 2's 16 bytes of the same copy, a pair ahead of
+  // their use, behind no wait of their own)
+  auto dma_site = [&](const Cand &c) {
+    dma_site_to_lds<SLOTS>(A.planes + (uint64_t)c.s2 * A.site_stride, lds_b, lane, 0, 1);
+    if (lane < (mom_on ? 3 : 2)) {
+      const char *src = reinterpret_cast<const char *>(A.sc4 + 4 * (uint64_t)c.s2) + lane * 16;
+      if (!MASKED && lane == 2) src = reinterpret_cast<const char *>(A.moments + 2 * c.rec);
+      __builtin_amdgcn_global_load_lds((glb_void_t *)src, (lds_void_t *)(lds_b + kSiteBytes), 16, 0, 0);
+    }
   };
   auto flush = [&](uint32_t n) {  // lane t derives and writes the record of ring entry t
     if ((uint32_t)lane < n) {
@@ -118,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
   };
 
   Cand cur = claim_next();
-  if (cur.ok) dma_site(cur.s2);
+  if (cur.ok) dma_site(cur);
   uint32_t held = 0;
   while (cur.ok) {
     const Cand nxt = claim_next();
@@ -131,8 +144,11 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     double sxy;
     const Relabel rl = relabel(m1, m2, mean1, mean2);
     double s12 = 0.0;
-    const bool dose1 = first_on && !skip && S1 >= 0.0;  // (wavefront-uniform) the row is dose_ok
-    if (dose1) {  // this lane's share of sum d1 d2, before P takes the registers
+    const bool ok1 = has_ok && !skip && S1 >= 0.0;  // (wavefront-uniform) the row is dose_ok
+    const bool dose1 = first_on && ok1;
+    const bool bad1 = has_ok && S1 == -1.0;  // not dose_ok by itself (-2: by site_skip_kernel's mark alone, ld_prep.hip)
+    const bool want2 = (dose1 || (mom_on && has_ok && !bad1));  // the candidate's sum: for the step, or to tell what it is
+    if (dose1 && !mom_on) {  // this lane's share of sum d1 d2, before P takes the registers
       const DoseWeights u = dose_weights(rl.m2);
       const double *d1 = reinterpret_cast<const double *>(smem + kDoseOff) + lane;
       const double *pb = reinterpret_cast<const double *>(lds_b) + lane;
@@ -152,9 +168,33 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     stage_pair<SLOTS, MASKED, !MASKED, true>(reinterpret_cast<const double *>(lds_a), kNp, (uint32_t)lane,
                                              reinterpret_cast<const double *>(lds_b), kNp, (uint32_t)lane, (uint32_t)lane,
                                              A.n_ind, rl.mean1, rl.mean2, P, vbits, sxy, rl.flip1, rl.flip2);
+    // stage_pair's own moment, in its operations and order (this call's is dead code then): the lane's share
+    auto moment_of_P = [&]() -> double {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j) t += fma(4.0, P[j][8], fma(2.0, P[j][5] + P[j][7], P[j][4]));
+      return t;
+    };
+    if (!MASKED && !mom_on) sxy = moment_of_P();
+    // (the same for the rare pair below, behind an empty statement per slot: left to itself the compiler forms ONE lane share
+    // for both uses, in front of the branches -- 32 VALU instructions and a VGPR pair on every pair of the launch)
+    auto moment_of_P_apart = [&]() -> double {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j) {
+        double p8 = P[j][8];
+        asm volatile("" : "+v"(p8));
+        t += fma(4.0, p8, fma(2.0, P[j][5] + P[j][7], P[j][4]));
+      }
+      return t;
+    };
+    if (!MASKED && mom_on) {  // {sum e1 e2, sum d1 d2}, the same in every lane: the last reads of the buffer
+      sxy = sc[4];
+      if (dose1) s12 = sc[5];
+    }
     // all ds_reads of the buffer are consumed (P is computed): start the copy of the next site over it
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (nxt.ok) dma_site(nxt.s2);
+    if (nxt.ok) dma_site(nxt);
     const uint32_t x = MASKED ? count_valid<SLOTS>(vbits) : A.n_ind;
     const double inv_x = MASKED ? 1.0 / (double)x : A.inv_n;
     // The candidate's dosage sum, through the SCALAR cache: the address is wavefront-uniform, and a vector load here would
@@ -163,15 +203,21 @@ __global__ __launch_bounds__(256, 2) void pair_ld_run_kernel(PairArgs A) {
     // kernel writes global memory); issued here, waited for after the Pearson moment's reduction.
     // (The empty statement pins the lane's share of the moment in front of the load: the compiler's own wait for
     // stage_pair's LDS reads, which it places at their first use, would otherwise come right behind the load.)
-    double S2 = -1.0;
+    double S2 = -2.0;  // (not asked for: no step, and nothing said about the site)
     if constexpr (kFirst) {
-      asm volatile("" : "+v"(sxy));
-      if (dose1) asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(S2) : "s"(A.dose_sum + cur.s2) : "memory");
+      if (!mom_on) asm volatile("" : "+v"(sxy));
+      if (want2) asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(S2) : "s"(A.dose_ok + cur.s2) : "memory");
     }
-    sxy = fma(-(double)A.n_ind * rl.mean1, rl.mean2, wave_sum1_bcast(sxy));  // centred: sum e1 e2 - n mean1 mean2
+    if (MASKED || !mom_on) sxy = wave_sum1_bcast(sxy);
     if constexpr (kFirst) {
-      if (dose1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(S2)::"memory");
+      if (want2) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(S2)::"memory");
+      // A pair with a site that by itself takes no part in the first step (not dose_ok: -1) keeps the in-kernel moment: its
+      // records are the same bits whether the pass ran or not, whether the step is on or not, and -- a marked site is -2 or a
+      // sum, never -1 -- whether the marks are on or not (tests/test_gpu_pair_moments.py, tests/test_gpu_first_step.py,
+      // tests/test_gpu_replay_lkl.py).  Wavefront-uniform, rare.
+      if (mom_on && has_ok && (bad1 || S2 == -1.0)) sxy = wave_sum1_bcast(moment_of_P_apart());
     }
+    sxy = fma(-(double)A.n_ind * rl.mean1, rl.mean2, sxy);  // centred: sum e1 e2 - n mean1 mean2
     double f0, f1, f2, f3;
     uint32_t n_iter = 0;
     if (skip) {  // (wavefront-uniform)

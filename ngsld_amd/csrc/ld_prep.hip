@@ -490,12 +490,16 @@ hipError_t launch_pack_scalars(const double *maf, const double *mean_e, const do
 // The per-site half of the run kernel's first EM step from dosages (ld_kernel_run.h): dose_sum[s] = sum_i d_i, the posterior
 // dosages of the site's individuals under HWE weights at the site's frequency -- the very double that goes into sc4[.][0], under
 // the labels the pair kernels give the site (Relabel: a frequency above 1/2 is 1 - m with planes 0 and 2 trading places) -- or
-// -1 where the site is not dose_ok and its pairs keep the per-individual first step:
+// a negative number where the site is not dose_ok and its pairs keep the per-individual first step (-1, or -2 for the last reason alone):
 //   * the frequency is not strictly inside (0, 1);
 //   * some individual's den = u . a (dose_terms: the kernel's own order of operations) is below kDoseDenMin or not finite, or
 //     its dosage is not finite.  The floor keeps the product of two dens -- the reference's s of that individual at linkage
 //     equilibrium -- a normal double: where the reference's s underflows to 0 (four NaNs, nIter 0) the pair must not be
 //     given a finite first step, and with one site out it is not (tests/test_gpu_first_step_alone.py);
+//   * the product of the dens of one lane's individuals (i, i + 64, ...: the run kernel's slots) is below kDoseDenMin^2: the
+//     in-kernel form of the candidate's dosages (NGSLD_TEST_PAIR_MOMENTS=0, ld_kernel_run.h) shares one reciprocal among them
+//     and gives NaN where that product leaves the double range -- pair_ld_moments_kernel divides per individual and would
+//     take the step there.  With such a site out both forms start its pairs alike (nIter, tests/test_gpu_first_step_alone.py);
 //   * a triple does not sum to 1 (odd_triple: what signed_rsx looks for, at either label);
 //   * site_skip_kernel marked the site degenerate.
 // One wavefront per site; the sum in a FIXED order: a lane's individuals in slot order, then wave_sum1 over the lanes.
@@ -511,8 +515,9 @@ __global__ __launch_bounds__(256) void site_dose_kernel(const double *__restrict
     const double m = flip ? 1.0 - m_in : m_in;
     const DoseWeights u = dose_weights(m);
     const double *p0 = pl + (flip ? 2ull * np : 0ull), *p1 = pl + np, *p2 = pl + (flip ? 0ull : 2ull * np);
-    bool ok = m_in > 0.0 && m_in < 1.0 && !(skip != nullptr && skip[site]);
-    double acc = 0.0;
+    bool ok = m_in > 0.0 && m_in < 1.0;
+    const bool marked = skip != nullptr && skip[site];
+    double acc = 0.0, prod = 1.0;
     for (uint32_t i = (uint32_t)lane; i < n_ind; i += 64) {
       const double a0 = p0[i], a1 = p1[i], a2 = p2[i];
       double den, num;
@@ -520,10 +525,14 @@ __global__ __launch_bounds__(256) void site_dose_kernel(const double *__restrict
       const double d = num / den;
       ok = ok && den >= kDoseDenMin && den < __builtin_inf() && d >= 0.0 && d < __builtin_inf() && !odd_triple(a0, a1, a2);
       acc += d;
+      prod *= den;
     }
+    ok = ok && prod >= kDoseDenMin * kDoseDenMin;
     const double S = wave_sum1(acc);
     const bool all_ok = __ballot(!ok) == 0 && S >= 0.0 && S < __builtin_inf();
-    if (lane == 0) dose_sum[site] = all_ok ? S : -1.0;
+    // (-2: nothing but the mark keeps the site out -- the run kernel tells the two apart where it chooses a pair's Pearson
+    // moment, which must not depend on whether the marks are on: ld_kernel_run.h)
+    if (lane == 0) dose_sum[site] = all_ok ? (marked ? -2.0 : S) : -1.0;
   }
 }
 
