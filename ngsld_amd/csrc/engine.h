@@ -4,6 +4,7 @@
 //   engine_plan.hip    the pair-space plan: the s2 walk of calc_pair_LD for every s1 (ngsLD.cpp:240-282), items, runs
 //   engine_run.hip     ngsld_run / ngsld_run_device: batches, pair-kernel launches, device-side TSV
 //   engine_replay.hip  exact-order replay: flag lists, host threads, the device-side replays, the exact-value store
+//   record_pass.hip    the host frame of the record passes (record_pass.h)
 #pragma once
 
 #include "knobs.h"
@@ -546,6 +547,13 @@ inline int hip_fail(ngsld_ctx *c, hipError_t e, const char *what) {
     if (e_ != hipSuccess) return hip_fail(c, e_, #call); \
   } while (0)
 
+// the same for a call that answers with an NGSLD_* code of its own (its message is set already)
+#define RC_TRY(call)                     \
+  do {                                   \
+    const int rc_ = (call);              \
+    if (rc_ != NGSLD_OK) return rc_;     \
+  } while (0)
+
 // No exception crosses the C-ABI (include/ngsld.h): every entry point that allocates host memory is a function-try-block
 // ending in this handler.  Work still in flight is waited for, so that buffers the caller owns are quiet on return.
 inline int caught(ngsld_ctx *c, bool nomem) {
@@ -587,6 +595,13 @@ void plan_rows(const std::vector<double> &pos_dist, const std::vector<double> &m
 int build_runs(ngsld_ctx *c, uint64_t run_len, const std::vector<uint64_t> &launch_ends);
 
 // ---- engine_run.hip ----
+// Where a cut of consecutive rows that begins at r0 ends: the rows up to `end` while the next one still fits `target` entries of
+// `off` (h_row_off: pairs; h_item_off: items).  A row is never cut: one longer than `target` is a cut of its own.
+inline uint64_t rows_within(const std::vector<uint64_t> &off, uint64_t r0, uint64_t end, uint64_t target) {
+  uint64_t r1 = r0 + 1;
+  while (r1 < end && off[r1 + 1] - off[r0] <= target) ++r1;
+  return r1;
+}
 hipError_t timed_launch(ngsld_ctx *c, const PairArgs &a, hipStream_t stream);
 // flag_n: records the flag buffer was laid out for (its two bitmaps follow the list: ld_device.h)
 PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext,

@@ -2,8 +2,6 @@
 // device-side TSV -> sink (replaces threadpool_add(calc_pair_LD) ... threadpool_wait and the fprintf block,
 // ngsLD.cpp:153-198, 310-352).
 #include "engine.h"
-#include "ld_prune.h"
-#include "record_pass.h"
 #include "../../include/ngsld_host.h"
 
 namespace ngsld {
@@ -60,8 +58,7 @@ static hipError_t launch_run_with_moments(ngsld_ctx *c, const PairArgs &a, hipSt
   cap = std::min(cap, want);
   const bool masked = false;
   for (uint64_t r0 = a.row0; r0 < a.row1;) {
-    uint64_t r1 = r0 + 1;
-    while (r1 < a.row1 && ro[r1 + 1] - ro[r0] <= cap) ++r1;
+    const uint64_t r1 = rows_within(ro, r0, a.row1, cap);
     if (ro[r1] > ro[r0]) {
       MomentArgs m{};
       m.planes = a.planes;
@@ -238,10 +235,8 @@ int ngsld_run_device(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, void *d_s
   const uint64_t max_items = 0x7ffffff0ull;
   std::vector<uint64_t> cuts;  // rows at which the launches end
   for (uint64_t r0 = s1_begin; r0 < s1_end;) {
-    uint64_t r1 = r0 + 1;
-    while (r1 < s1_end && c->h_item_off[r1 + 1] - c->h_item_off[r0] <= max_items) ++r1;
-    cuts.push_back(r1);
-    r0 = r1;
+    r0 = rows_within(c->h_item_off, r0, s1_end, max_items);
+    cuts.push_back(r0);
   }
   if (uses_runs(c->cfg.kernel)) {  // (big launches: whole-row runs, whatever an earlier ngsld_run cut them to, short ones at each launch's end)
     const int rcr = build_runs(c, kRunItems, cuts);
@@ -342,266 +337,313 @@ static int upload_text_prefix(ngsld_ctx *c, bool *text) {
   return NGSLD_OK;
 }
 
-// Rows [s1_begin, s1_end) through the batch pipeline: pair kernels, replay, text or records, sink -- batch by batch.
-static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn sink, void *user) {
-  const bool ext = c->params.extend_out != 0;
-  c->ev_used = 0;
-  c->timed_stream = c->stream;
-  c->timed_pairs = c->h_row_off[s1_end] - c->h_row_off[s1_begin];
-  c->replayed_pairs = 0;
-  c->replayed_on_device = 0;
-  c->flagged_pairs = 0;
-  c->text_rows_patched = 0;
-  const bool replay = c->replay_on;
-  if (c->reserve_thread.joinable()) c->reserve_thread.join();  // (ngsld_reserve_text_buffers: h_text[] is this thread's again)
+// ---- what the batch pipeline (BatchRun) and the groups (run_grouped) share ----
+// The TextArgs of rows [r0, r1), n pairs: the batch's records, where its rows' lengths, their prefix sums and the text go, its two
+// marks (text_cap 0: the write pass is not checked against the buffer unless the caller says so).
+static TextArgs make_text_args(const ngsld_ctx *c, uint64_t r0, uint64_t r1, uint64_t n, const ngsld_rec_std *std_rec, const ngsld_rec_ext *ext_rec,
+                               uint64_t *lens, uint64_t *offs, char *text, int *needs_host, uint64_t *overflow) {
+  TextArgs t{};
+  t.items = c->d_items.p + c->h_item_off[r0];
+  t.n_items = c->h_item_off[r1] - c->h_item_off[r0];
+  t.out_base = c->h_row_off[r0];
+  t.n_pairs = n;
+  t.std_rec = std_rec;
+  t.ext_rec = ext_rec;
+  t.maf = c->d_maf.p;
+  t.cum = c->d_cum.p;
+  t.infc = c->d_infc.p;
+  t.labels = c->have_labels ? c->d_labels.p : nullptr;
+  t.label_off = c->d_label_off.p;
+  t.lens = lens;
+  t.offs = offs;
+  t.text = text;
+  t.text_cap = 0;
+  t.overflow = overflow;
+  t.needs_host = needs_host;
+  return t;
+}
 
-  bool text = c->text_mode;
-  if (text) {
-    const int rct = upload_text_prefix(c, &text);
-    if (rct != NGSLD_OK) return rct;
+// n records (with --extend_out both kinds) from device memory into slot k's pinned host buffers, on `stream`
+static hipError_t copy_records_to_host(ngsld_ctx *c, int k, const ngsld_rec_std *src_std, const ngsld_rec_ext *src_ext, uint64_t n, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const hipError_t e = hipMemcpyAsync(c->h_std[k].p, src_std, n * sizeof(ngsld_rec_std), hipMemcpyDeviceToHost, stream);
+  if (e != hipSuccess || c->params.extend_out == 0) return e;
+  return hipMemcpyAsync(c->h_ext[k].p, src_ext, n * sizeof(ngsld_rec_ext), hipMemcpyDeviceToHost, stream);
+}
+
+// the items of rows [r0, r1) for the sink, first_record made relative to the batch (ensure_host_items has run)
+static void relative_items(const ngsld_ctx *c, uint64_t r0, uint64_t r1, std::vector<Item> &rel_items, ngsld_batch &out) {
+  const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
+  rel_items.assign(c->h_items.begin() + (ptrdiff_t)i0, c->h_items.begin() + (ptrdiff_t)i1);
+  for (auto &it : rel_items) it.first_record -= c->h_row_off[r0];
+  out.n_items = i1 - i0;
+  out.items = rel_items.data();
+}
+
+static bool text_fallback_forced(uint64_t index) {  // tests: every n-th text batch takes the record path
+  const char *e = test_knob("TEXT_FALLBACK_EVERY");
+  const uint64_t every = e != nullptr ? std::strtoull(e, nullptr, 10) : 0;
+  return every > 0 && index % every == every - 1;
+}
+
+// The one way out of a loop that enqueues: these streams are waited for whatever `rc` is -- nothing of the run stays pending
+// behind an error, in buffers the next call resizes -- and the first error is the one reported.
+static int drain(ngsld_ctx *c, int rc, std::initializer_list<hipStream_t> streams) {
+  for (hipStream_t s : streams) {
+    const hipError_t e = s != nullptr ? hipStreamSynchronize(s) : hipSuccess;
+    if (rc == NGSLD_OK && e != hipSuccess) rc = hip_fail(c, e, "hipStreamSynchronize at the end of a run");
   }
-  auto need_host_items = [&]() -> int { return ensure_host_items(c); };
-  if (!text) {  // (record batches carry their items to the sink; text batches need none -- the replay finds its pairs on the device)
-    const int rc0 = need_host_items();
-    if (rc0 != NGSLD_OK) return rc0;
-  }
-  // How the batches flow: two slots, the kernel of batch k + 1 runs while batch k is consumed.  Text: the rows are formatted
-  // on the device and copied.  Records: the pair kernels write them straight into the slot's pinned host buffers
-  // (run_direct; nothing is left to copy behind the last kernel; twice the pairs per batch, half the launches), or into
-  // device buffers with a D2H copy per batch, the batches then shrinking towards the end of the run (run_taper).
-  // NGSLD_TEST_RUN_STREAMS=2: three slots, two compute streams half a batch out of phase (see ngsld_ctx).
-  const bool direct = !text && c->run_direct;
-  // Text batches are small (2^19 rows: a 2.8 ms pair kernel, a tenth of it ramp and drain) and many: for them the two compute
-  // streams half a batch out of phase DO pay, on every box -- while one stream's kernel drains the other's is in full
-  // flight: configs[2]'s loop 0.58-0.63 -> 0.546-0.551 s (profiles/r04/e2e_text_streams.txt).  (tests: NGSLD_TEST_TEXT_STREAMS=1: one stream.)
-  bool text_two = true;
-  if (const char *e = test_knob("TEXT_STREAMS")) text_two = std::atoi(e) != 1;
-  const bool two_streams = text ? text_two : c->run_streams == 2;
-  c->timed_overlap = two_streams;  // (ngsld_last_kernel_time: launches on two streams share the device -- first start .. last end)
-  // (text on ONE stream with three slots, two batches queued ahead, measured no different from two slots: the compute stream
-  // does not run dry, profiles/r04/e2e_timeline.txt)
-  const int S = two_streams ? ngsld_ctx::kSlots : 2;
+  return rc;
+}
+
+static int finish_run(ngsld_ctx *c) {
+  bool have = false;  // (the store's builder is still at the sites behind this run's rows: its errors are this run's)
+  if (c->exact_state.load() == 1) RC_TRY(wait_exact_store(c, c->n_sites, &have));
+  return check_status(c);
+}
+
+// Rows [s1_begin, s1_end) through the batch pipeline: pair kernels, replay, text or records, sink -- batch by batch.
+// How the batches flow: two slots, the kernel of batch k + 1 runs while batch k is consumed.  Text: the rows are formatted
+// on the device and copied.  Records: the pair kernels write them straight into the slot's pinned host buffers
+// (run_direct; nothing is left to copy behind the last kernel; twice the pairs per batch, half the launches), or into
+// device buffers with a D2H copy per batch, the batches then shrinking towards the end of the run (run_taper).
+// NGSLD_TEST_RUN_STREAMS=2: three slots, two compute streams half a batch out of phase (see ngsld_ctx).
+struct BatchRun {
   struct Batch {
     uint64_t r0, r1, n;
   };
+  ngsld_ctx *const c;
+  const uint64_t s1_begin, s1_end;
+  const ngsld_sink_fn sink;
+  void *const user;
+  const bool ext, replay, text, direct;  // direct: the pair kernels write the records into the pinned host buffers themselves
+  bool two_streams;
+  int S;                 // slots in use
+  uint64_t batch_pairs;  // the batches' target
+  uint64_t cap = 1;      // pairs of the largest batch: what every slot's buffers hold
+  size_t scan_bytes = 0;
   std::vector<Batch> batches;
-  // text batches are cut sixteen times finer: smaller batches mean smaller pinned buffers and a finer kernel / copy overlap
-  // (kTextBatchPairs; round 1, configs[2] end to end: 2^23 pairs per batch 2.2 s, 2^21 1.5 s)
-  // (records written by the kernels themselves: every launch costs ~0.4 ms of drain and nothing has to be staged on the
-  // device, so the batches are twice the size -- 2 x 1.2 GB of pinned host memory with the extended record)
-  const uint64_t text_batch = kTextBatchPairs;
-  uint64_t batch_pairs = text ? std::min<uint64_t>(c->batch_pairs, text_batch)
-                              : ((direct && !c->batch_pairs_set) ? 2 * c->batch_pairs : c->batch_pairs);
-  const bool taper = !text && !direct && c->run_taper;
-  uint64_t cap = 1, last_cap = 0;
-  for (;;) {  // (a second trip only when the pinned record buffers of this batch size cannot be had: half the size then)
-    batches.clear();
-    uint64_t left = c->timed_pairs;
-    for (uint64_t r0 = s1_begin; r0 < s1_end;) {
-      uint64_t target = batch_pairs;
-      if (two_streams && batches.empty()) target = batch_pairs / 2;  // (the phase shift between the two streams)
-      if (taper) target = std::min<uint64_t>(batch_pairs, std::max<uint64_t>(left / 3, std::min<uint64_t>(batch_pairs, 1ull << 19)));
-      uint64_t r1 = r0 + 1;
-      while (r1 < s1_end && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= target) ++r1;
-      batches.push_back({r0, r1, c->h_row_off[r1] - c->h_row_off[r0]});
-      left -= std::min(left, c->h_row_off[r1] - c->h_row_off[r0]);
-      r0 = r1;
-    }
-    cap = 1;
-    for (auto &b : batches) cap = std::max(cap, b.n);
-    if (text) break;
-    // the batches' host buffers: pinned memory is the scarce kind -- a host that cannot pin two (three) buffers of this size
-    // gets batches of half the size instead of an error, down to 2^20 pairs
-    hipError_t e = hipSuccess;
-    if (const char *lim = test_knob("PIN_LIMIT_BYTES"))  // tests: a host that cannot pin more than this per buffer
-      if (cap * sizeof(ngsld_rec_std) > std::strtoull(lim, nullptr, 10)) e = hipErrorOutOfMemory;
-    for (int k = 0; k < S && e == hipSuccess; ++k) {
-      e = c->h_std[k].resize(cap);
-      if (e == hipSuccess && ext) e = c->h_ext[k].resize(cap);
-    }
-    if (e == hipSuccess) break;
-    (void)hipGetLastError();
-    // (a batch holds at least one row: once the largest row is what sets `cap`, halving the target changes nothing)
-    if (cap <= (1ull << 16) || batches.size() >= (1u << 20) || cap == last_cap || batch_pairs <= 1)
-      return hip_fail(c, e, "pinned host buffers of a record batch");
-    last_cap = cap;
-    batch_pairs = std::min(batch_pairs, cap);  // (a run smaller than a batch: halve what it actually needed)
-    for (int k = 0; k < S; ++k) {
-      c->h_std[k].release();
-      c->h_ext[k].release();
-    }
-    batch_pairs /= 2;
+  // a slot's records as the pair kernels address them (run_direct: the device addresses of the pinned host buffers)
+  ngsld_rec_std *dev_std[ngsld_ctx::kSlots] = {nullptr, nullptr, nullptr};
+  ngsld_rec_ext *dev_ext[ngsld_ctx::kSlots] = {nullptr, nullptr, nullptr};
+  const bool trace = std::getenv("NGSLD_TRACE") != nullptr;  // dev: per-batch host timeline on stderr
+  const std::chrono::steady_clock::time_point t_run = std::chrono::steady_clock::now();
+  double t_a = 0.0, t_b = 0.0, t_ev = 0.0, t_wr = 0.0;  // ms: the next batch issued t_a..t_b, this one's kernels done, its text on the host
+  const bool host_patch_on = !test_knob_is("TEXT_HOST_PATCH", "0");  // tests: 0 = the replayed rows through the device again, the fallback of a patch that does not fit
+  uint64_t patch_fail_every = 0;  // tests: every n-th patched batch pretends its last row changed length (the fallback's way out)
+  uint64_t patched_batches = 0;
+  // scratch, kept from batch to batch
+  std::vector<Item> rel_items;                        // a batch that goes out as records: its items for the sink
+  std::vector<uint64_t> recs;                         // both arms: the batch's records left to the host's replay (flagged_records)
+  std::vector<uint32_t> rep_s1, rep_s2;               // consume_text: their sites (find_flag_rows, or replay_flagged in device_patch)
+  std::vector<uint32_t> hp_row;                       // find_flag_rows -> apply_host_patch: recs[j]'s entry of the slot's h_flag_rows
+  std::vector<std::pair<uint64_t, uint32_t>> by_rec;  // find_flag_rows: the slot's list by record
+  std::vector<ngsld_rec_std> hp_std;                  // consume_text -> apply_host_patch: the pairs as the host replayed them
+  std::vector<ngsld_rec_ext> hp_ext;
+
+  BatchRun(ngsld_ctx *ctx, uint64_t r_begin, uint64_t r_end, ngsld_sink_fn sink_fn, void *sink_user, bool as_text)
+      : c(ctx), s1_begin(r_begin), s1_end(r_end), sink(sink_fn), user(sink_user), ext(ctx->params.extend_out != 0), replay(ctx->replay_on),
+        text(as_text), direct(!as_text && ctx->run_direct) {
+    // Text batches are small (2^19 rows: a 2.8 ms pair kernel, a tenth of it ramp and drain) and many: for them the two compute
+    // streams half a batch out of phase DO pay, on every box -- while one stream's kernel drains the other's is in full
+    // flight: configs[2]'s loop 0.58-0.63 -> 0.546-0.551 s (profiles/r04/e2e_text_streams.txt).  (tests: NGSLD_TEST_TEXT_STREAMS=1: one stream.)
+    bool text_two = true;
+    if (const char *e = test_knob("TEXT_STREAMS")) text_two = std::atoi(e) != 1;
+    two_streams = text ? text_two : c->run_streams == 2;
+    c->timed_overlap = two_streams;  // (ngsld_last_kernel_time: launches on two streams share the device -- first start .. last end)
+    // (text on ONE stream with three slots, two batches queued ahead, measured no different from two slots: the compute stream
+    // does not run dry, profiles/r04/e2e_timeline.txt)
+    S = two_streams ? ngsld_ctx::kSlots : 2;
+    // text batches are cut sixteen times finer: smaller batches mean smaller pinned buffers and a finer kernel / copy overlap
+    // (kTextBatchPairs; round 1, configs[2] end to end: 2^23 pairs per batch 2.2 s, 2^21 1.5 s)
+    // (records written by the kernels themselves: every launch costs ~0.4 ms of drain and nothing has to be staged on the
+    // device, so the batches are twice the size -- 2 x 1.2 GB of pinned host memory with the extended record)
+    const uint64_t text_batch = kTextBatchPairs;
+    batch_pairs = text ? std::min<uint64_t>(c->batch_pairs, text_batch) : ((direct && !c->batch_pairs_set) ? 2 * c->batch_pairs : c->batch_pairs);
+    if (const char *e = test_knob("TEXT_HOST_PATCH_FAIL_EVERY")) patch_fail_every = std::strtoull(e, nullptr, 10);
   }
-  if (uses_runs(c->cfg.kernel)) {
+  double now_ms() const { return ms_since(t_run); }
+  int slot_of(size_t bi) const { return (int)(bi % (size_t)S); }
+
+  // The batches, and for record batches the slots' pinned host buffers.
+  int plan_batches() {
+    const bool taper = !text && !direct && c->run_taper;
+    uint64_t last_cap = 0;
+    for (;;) {  // (a second trip only when the pinned record buffers of this batch size cannot be had: half the size then)
+      batches.clear();
+      uint64_t left = c->timed_pairs;
+      for (uint64_t r0 = s1_begin; r0 < s1_end;) {
+        uint64_t target = batch_pairs;
+        if (two_streams && batches.empty()) target = batch_pairs / 2;  // (the phase shift between the two streams)
+        if (taper) target = std::min<uint64_t>(batch_pairs, std::max<uint64_t>(left / 3, std::min<uint64_t>(batch_pairs, 1ull << 19)));
+        const uint64_t r1 = rows_within(c->h_row_off, r0, s1_end, target);
+        batches.push_back({r0, r1, c->h_row_off[r1] - c->h_row_off[r0]});
+        left -= std::min(left, c->h_row_off[r1] - c->h_row_off[r0]);
+        r0 = r1;
+      }
+      cap = 1;
+      for (auto &b : batches) cap = std::max(cap, b.n);
+      if (text) break;
+      // the batches' host buffers: pinned memory is the scarce kind -- a host that cannot pin two (three) buffers of this size
+      // gets batches of half the size instead of an error, down to 2^20 pairs
+      hipError_t e = hipSuccess;
+      if (const char *lim = test_knob("PIN_LIMIT_BYTES"))  // tests: a host that cannot pin more than this per buffer
+        if (cap * sizeof(ngsld_rec_std) > std::strtoull(lim, nullptr, 10)) e = hipErrorOutOfMemory;
+      for (int k = 0; k < S && e == hipSuccess; ++k) {
+        e = c->h_std[k].resize(cap);
+        if (e == hipSuccess && ext) e = c->h_ext[k].resize(cap);
+      }
+      if (e == hipSuccess) break;
+      (void)hipGetLastError();
+      // (a batch holds at least one row: once the largest row is what sets `cap`, halving the target changes nothing)
+      if (cap <= (1ull << 16) || batches.size() >= (1u << 20) || cap == last_cap || batch_pairs <= 1)
+        return hip_fail(c, e, "pinned host buffers of a record batch");
+      last_cap = cap;
+      batch_pairs = std::min(batch_pairs, cap);  // (a run smaller than a batch: halve what it actually needed)
+      for (int k = 0; k < S; ++k) {
+        c->h_std[k].release();
+        c->h_ext[k].release();
+      }
+      batch_pairs /= 2;
+    }
+    return NGSLD_OK;
+  }
+
+  int build_runs() {
+    if (!uses_runs(c->cfg.kernel)) return NGSLD_OK;
     // every batch should be thousands of workgroups (512 run at a time): the smaller the batches, the shorter the runs.
     // configs[2] as text (48 batches of 2^21 pairs): 16 items per run 0.82 s for this loop, 8 0.72 s, 4 0.70 s
     uint64_t want = kRunItems;
     while (want > 2 && want * item_span(c->cfg, c->pairs_per_item) * 8192 > batch_pairs) want /= 2;
     std::vector<uint64_t> ends;  // every batch is a launch: its last rows go out as short runs (build_runs)
     for (auto &b : batches) ends.push_back(b.r1);
-    const int rcr = build_runs(c, want, ends);
-    if (rcr != NGSLD_OK) return rcr;
+    return eng::build_runs(c, want, ends);
   }
-  for (int k = 0; k < S; ++k) {
-    if (!direct) {
-      HIP_TRY(c, c->d_std[k].resize(cap));
-      if (ext) HIP_TRY(c, c->d_ext[k].resize(cap));
+
+  // The slots' device, text and flag buffers for batches of `cap` pairs, the records' device addresses, the text stream, the
+  // events, the scan space.
+  int reserve_slots() {
+    for (int k = 0; k < S; ++k) {
+      if (!direct) {
+        HIP_TRY(c, c->d_std[k].resize(cap));
+        if (ext) HIP_TRY(c, c->d_ext[k].resize(cap));
+        dev_std[k] = c->d_std[k].p;
+        dev_ext[k] = ext ? c->d_ext[k].p : nullptr;
+      } else {  // (run_direct: the device addresses of the pinned host buffers -- the same numbers under unified addressing, asked for anyway)
+        HIP_TRY(c, hipHostGetDevicePointer((void **)&dev_std[k], c->h_std[k].p, 0));
+        if (ext) HIP_TRY(c, hipHostGetDevicePointer((void **)&dev_ext[k], c->h_ext[k].p, 0));
+      }
+      if (text) {
+        HIP_TRY(c, c->d_lens[k].resize(cap));
+        HIP_TRY(c, c->d_offs[k].resize(cap));
+        HIP_TRY(c, c->d_text_meta[k].resize(4));  // {total bytes, needs_host, a replayed row changed its length, the early write pass ran out of room}
+        HIP_TRY(c, c->h_text_meta[k].resize(4));
+        // the batch's rows are WRITTEN right behind their lengths, on the compute stream, before the host knows how long the
+        // text is (see issue): room for the usual row -- a batch that needs more is written again once its length is known
+        const uint64_t row_guess = 2 * c->max_label + (ext ? 200 : 72);
+        if (c->d_text[k].n < cap * row_guess) HIP_TRY(c, c->d_text[k].resize(cap * row_guess));
+      }
+      if (replay) {
+        c->flag_cap[k] = flag_cap_for(cap);
+        HIP_TRY(c, c->d_flags[k].resize(flag_words(cap, c->flag_cap[k])));
+        HIP_TRY(c, c->h_flags[k].resize(flag_head_words(c->flag_cap[k])));
+        if (text) HIP_TRY(c, c->h_flag_rows[k].resize(kFlagRowsCap));
+      }
     }
     if (text) {
-      HIP_TRY(c, c->d_lens[k].resize(cap));
-      HIP_TRY(c, c->d_offs[k].resize(cap));
-      HIP_TRY(c, c->d_text_meta[k].resize(4));  // {total bytes, needs_host, a replayed row changed its length, the early write pass ran out of room}
-      HIP_TRY(c, c->h_text_meta[k].resize(4));
-      // the batch's rows are WRITTEN right behind their lengths, on the compute stream, before the host knows how long the
-      // text is (see issue): room for the usual row -- a batch that needs more is written again once its length is known
-      const uint64_t row_guess = 2 * c->max_label + (ext ? 200 : 72);
-      if (c->d_text[k].n < cap * row_guess) HIP_TRY(c, c->d_text[k].resize(cap * row_guess));
+      if (c->text_stream == nullptr) HIP_TRY(c, hipStreamCreate(&c->text_stream));
+      for (int k = 0; k < S; ++k)
+        if (c->ev_scan_done[k] == nullptr) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scan_done[k], hipEventDisableTiming));
+      scan_bytes = text_scan_temp_bytes(cap);
+      HIP_TRY(c, c->d_scan_tmp.resize(scan_bytes ? scan_bytes : 1));
+      if (two_streams) HIP_TRY(c, c->d_scan_tmp_b.resize(scan_bytes ? scan_bytes : 1));
+      if (replay) HIP_TRY(c, c->d_scan_tmp2.resize(scan_bytes ? scan_bytes : 1));
     }
-    if (replay) {
-      c->flag_cap[k] = flag_cap_for(cap);
-      HIP_TRY(c, c->d_flags[k].resize(flag_words(cap, c->flag_cap[k])));
-      HIP_TRY(c, c->h_flags[k].resize(flag_head_words(c->flag_cap[k])));
-      if (text) HIP_TRY(c, c->h_flag_rows[k].resize(kFlagRowsCap));
-    }
+    return NGSLD_OK;
   }
-  // (run_direct: the device addresses of the pinned host buffers -- the same numbers under unified addressing, asked for anyway)
-  ngsld_rec_std *dev_std[ngsld_ctx::kSlots] = {nullptr, nullptr, nullptr};
-  ngsld_rec_ext *dev_ext[ngsld_ctx::kSlots] = {nullptr, nullptr, nullptr};
-  for (int k = 0; k < S; ++k) {
-    if (direct) {
-      HIP_TRY(c, hipHostGetDevicePointer((void **)&dev_std[k], c->h_std[k].p, 0));
-      if (ext) HIP_TRY(c, hipHostGetDevicePointer((void **)&dev_ext[k], c->h_ext[k].p, 0));
-    } else {
-      dev_std[k] = c->d_std[k].p;
-      dev_ext[k] = ext ? c->d_ext[k].p : nullptr;
-    }
+
+  TextArgs text_args(const Batch &b, int k) const {  // the text of slot k's batch from the slot's device records, into the slot's buffers
+    return make_text_args(c, b.r0, b.r1, b.n, c->d_std[k].p, ext ? c->d_ext[k].p : nullptr, c->d_lens[k].p, c->d_offs[k].p, c->d_text[k].p,
+                          reinterpret_cast<int *>(c->d_text_meta[k].p + 1), c->d_text_meta[k].p + 3);
   }
-  size_t scan_bytes = 0;
-  if (text) {
-    if (c->text_stream == nullptr) HIP_TRY(c, hipStreamCreate(&c->text_stream));
-    for (int k = 0; k < S; ++k)
-      if (c->ev_scan_done[k] == nullptr) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scan_done[k], hipEventDisableTiming));
-    scan_bytes = text_scan_temp_bytes(cap);
-    HIP_TRY(c, c->d_scan_tmp.resize(scan_bytes ? scan_bytes : 1));
-    if (two_streams) HIP_TRY(c, c->d_scan_tmp_b.resize(scan_bytes ? scan_bytes : 1));
-    if (replay) HIP_TRY(c, c->d_scan_tmp2.resize(scan_bytes ? scan_bytes : 1));
-  }
-  auto text_args = [&](const Batch &b, int k) -> TextArgs {
-    TextArgs t{};
-    t.items = c->d_items.p + c->h_item_off[b.r0];
-    t.n_items = c->h_item_off[b.r1] - c->h_item_off[b.r0];
-    t.out_base = c->h_row_off[b.r0];
-    t.n_pairs = b.n;
-    t.std_rec = c->d_std[k].p;
-    t.ext_rec = ext ? c->d_ext[k].p : nullptr;
-    t.maf = c->d_maf.p;
-    t.cum = c->d_cum.p;
-    t.infc = c->d_infc.p;
-    t.labels = c->have_labels ? c->d_labels.p : nullptr;
-    t.label_off = c->d_label_off.p;
-    t.lens = c->d_lens[k].p;
-    t.offs = c->d_offs[k].p;
-    t.text = c->d_text[k].p;
-    t.text_cap = 0;
-    t.overflow = c->d_text_meta[k].p + 3;
-    t.needs_host = reinterpret_cast<int *>(c->d_text_meta[k].p + 1);
-    return t;
-  };
-  std::vector<Item> rel_items;
-  std::vector<uint64_t> recs;
-  std::vector<uint32_t> rep_s1, rep_s2;
-  auto issue = [&](size_t bi) -> int {  // kernel on a compute stream; text: lengths behind it; records: D2H on `copy_stream`
+
+  int issue(size_t bi) {  // kernel on a compute stream; text: lengths behind it; records: D2H on `copy_stream`
     Range range_issue("ngsld:issue batch (pair kernel + D2H)");
-    const int k = (int)(bi % (size_t)S);
+    const int k = slot_of(bi);
     const Batch &b = batches[bi];
     hipStream_t st = (two_streams && (bi & 1)) ? c->stream2 : c->stream;
-    if (replay) {
-      const int rcf = reset_flags(c, c->d_flags[k], b.n, c->flag_cap[k], st);
-      if (rcf != NGSLD_OK) return rcf;
-    }
+    if (replay) RC_TRY(reset_flags(c, c->d_flags[k], b.n, c->flag_cap[k], st));
     PairArgs a = make_args(c, b.r0, b.r1, dev_std[k], dev_ext[k], replay ? c->d_flags[k].p : nullptr, c->flag_cap[k], b.n);
     HIP_TRY(c, timed_launch(c, a, st));
     c->slot_dev_applied[k] = false;
     if (replay) {  // (called genotypes: the flagged pairs settled on the device, before anything reads the records)
-      int rcd = device_replay(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, k);
-      if (rcd != NGSLD_OK) return rcd;
+      RC_TRY(device_replay(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, k));
       // (likelihoods: the same once the exact store is there -- a batch issued before that is settled when it is consumed)
-      if (lkl_device_eligible(c) && (exact_store_started(c) || exact_store_is_free(c))) {
-        rcd = try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, true, k,
-                                    &c->slot_dev_applied[k], exact_sites_needed(c, b.r0, b.r1));
-        if (rcd != NGSLD_OK) return rcd;
-      }
+      if (lkl_device_eligible(c) && (exact_store_started(c) || exact_store_is_free(c)))
+        RC_TRY(try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, true, k,
+                                     &c->slot_dev_applied[k], exact_sites_needed(c, b.r0, b.r1)));
     }
     // which pairs the kernel flagged for the exact-order replay (counter + list, 32 KB): known to the host with the batch.
     // On the kernel's own stream, right behind it: on the copy stream, behind the records, this small copy took 9 ms per
     // batch -- it goes through a copy kernel, and that waited for the next batch's pair kernel to leave it a CU
     // (a small KERNEL, not a copy: send_flag_head)
-    if (replay) {
-      const int rch = send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], st, !c->slot_dev_applied[k]);
-      if (rch != NGSLD_OK) return rch;
-    }
-    if (text) {  // row lengths and their prefix sums right behind the pair kernel, the rows behind those
-      HIP_TRY(c, hipMemsetAsync(c->d_text_meta[k].p, 0, 4 * sizeof(uint64_t), st));
-      TextArgs t = text_args(b, k);
-      HIP_TRY(c, launch_text_lengths(t, st));
-      HIP_TRY(c, text_scan(st == c->stream ? c->d_scan_tmp.p : c->d_scan_tmp_b.p, scan_bytes, c->d_lens[k].p, c->d_offs[k].p, b.n,
-                           c->d_text_meta[k].p, st));
-      // The rows themselves, at once: on a stream of their own that waits for this batch's prefix sums -- no trip through
-      // the host.  Rounds 1-4 wrote the rows from the host's side of the loop (on the copy stream, once the host had read the
-      // batch's length): with fewer hardware queues than busy streams (GPU_MAX_HW_QUEUES, or other streams in the process) that
-      // kernel was SUBMITTED behind the pair kernels of the next two batches, queued behind them, and the host waited for
-      // them before it issued more -- 0.55 s for configs[2]'s loop on four queues, 0.80 on two, 0.94 on one
-      // (profiles/r04/hw_queues_ab.txt).  Submitted here it stands before them in whatever queue it shares; the copy stream
-      // carries nothing but the D2H copies (SDMA).  A batch whose records are patched afterwards (host replay) or that
-      // outgrows the buffer is written again when consumed.
-      t.text_cap = c->d_text[k].n;
-      if (replay) {  // (the pairs left to the host: which they are, where their rows lie -- see consume)
-        const int rcw = send_flag_rows(c, c->d_flags[k].p, c->flag_cap[k], c->slot_dev_applied[k], c->d_offs[k].p, c->d_lens[k].p, b.n,
-                                       c->h_row_off[b.r0], c->h_flag_rows[k].p, st);
-        if (rcw != NGSLD_OK) return rcw;
-      }
-      HIP_TRY(c, hipEventRecord(c->ev_scan_done[k], st));
-      HIP_TRY(c, hipStreamWaitEvent(c->text_stream, c->ev_scan_done[k], 0));
-      HIP_TRY(c, launch_text_write(t, c->text_stream));
-      HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->text_stream));
-      HIP_TRY(c, hipEventRecord(c->ev_kernel_done[k], c->text_stream));
-      return NGSLD_OK;
-    }
+    if (replay) RC_TRY(send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], st, !c->slot_dev_applied[k]));
+    if (text) return issue_text(k, b, st);
     HIP_TRY(c, hipEventRecord(c->ev_kernel_done[k], st));
     if (direct) return NGSLD_OK;  // (the records are in host memory when the kernel is done)
     HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_kernel_done[k], 0));
-    if (b.n) {
-      HIP_TRY(c, hipMemcpyAsync(c->h_std[k].p, c->d_std[k].p, b.n * sizeof(ngsld_rec_std), hipMemcpyDeviceToHost,
-                                c->copy_stream));
-      if (ext)
-        HIP_TRY(c, hipMemcpyAsync(c->h_ext[k].p, c->d_ext[k].p, b.n * sizeof(ngsld_rec_ext), hipMemcpyDeviceToHost,
-                                  c->copy_stream));
-    }
+    HIP_TRY(c, copy_records_to_host(c, k, c->d_std[k].p, c->d_ext[k].p, b.n, c->copy_stream));
     HIP_TRY(c, hipEventRecord(c->ev_copy_done[k], c->copy_stream));
     return NGSLD_OK;
-  };
-  const auto t_run = std::chrono::steady_clock::now();
-  auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run).count(); };
-  // ---- what consuming a text batch is made of (see the loop below) ----
-  const bool host_patch_on = [] {
-    const char *e = test_knob("TEXT_HOST_PATCH");  // (tests: 0 = the replayed rows through the device again, the fallback of a patch that does not fit)
-    return e == nullptr || std::strcmp(e, "0") != 0;
-  }();
-  std::vector<ngsld_rec_std> hp_std;
-  std::vector<ngsld_rec_ext> hp_ext;
-  std::vector<uint32_t> hp_row;  // recs[j]'s entry of the slot's h_flag_rows
-  std::vector<std::pair<uint64_t, uint32_t>> by_rec;
-  auto batch_needs_host = [&](int k, size_t bi) -> bool {  // a value beyond the device formatter's fast path: the batch goes out as records
-    bool needs_host = (c->h_text_meta[k].p[1] & 0xffffffffull) != 0;
-    if (const char *e = test_knob("TEXT_FALLBACK_EVERY")) {  // tests: every n-th batch takes the record path
-      const uint64_t every = std::strtoull(e, nullptr, 10);
-      if (every > 0 && bi % every == every - 1) needs_host = true;
-    }
-    return needs_host;
-  };
+  }
+
+  // issue, text: row lengths and their prefix sums right behind the pair kernel, the rows behind those
+  int issue_text(int k, const Batch &b, hipStream_t st) {
+    HIP_TRY(c, hipMemsetAsync(c->d_text_meta[k].p, 0, 4 * sizeof(uint64_t), st));
+    TextArgs t = text_args(b, k);
+    HIP_TRY(c, launch_text_lengths(t, st));
+    HIP_TRY(c, text_scan(st == c->stream ? c->d_scan_tmp.p : c->d_scan_tmp_b.p, scan_bytes, c->d_lens[k].p, c->d_offs[k].p, b.n, c->d_text_meta[k].p, st));
+    // The rows themselves, at once: on a stream of their own that waits for this batch's prefix sums -- no trip through
+    // the host.  Rounds 1-4 wrote the rows from the host's side of the loop (on the copy stream, once the host had read the
+    // batch's length): with fewer hardware queues than busy streams (GPU_MAX_HW_QUEUES, or other streams in the process) that
+    // kernel was SUBMITTED behind the pair kernels of the next two batches, queued behind them, and the host waited for
+    // them before it issued more -- 0.55 s for configs[2]'s loop on four queues, 0.80 on two, 0.94 on one
+    // (profiles/r04/hw_queues_ab.txt).  Submitted here it stands before them in whatever queue it shares; the copy stream
+    // carries nothing but the D2H copies (SDMA).  A batch whose records are patched afterwards (host replay) or that
+    // outgrows the buffer is written again when consumed.
+    t.text_cap = c->d_text[k].n;
+    if (replay)  // (the pairs left to the host: which they are, where their rows lie -- see consume_text)
+      RC_TRY(send_flag_rows(c, c->d_flags[k].p, c->flag_cap[k], c->slot_dev_applied[k], c->d_offs[k].p, c->d_lens[k].p, b.n, c->h_row_off[b.r0],
+                            c->h_flag_rows[k].p, st));
+    HIP_TRY(c, hipEventRecord(c->ev_scan_done[k], st));
+    HIP_TRY(c, hipStreamWaitEvent(c->text_stream, c->ev_scan_done[k], 0));
+    HIP_TRY(c, launch_text_write(t, c->text_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->text_stream));
+    HIP_TRY(c, hipEventRecord(c->ev_kernel_done[k], c->text_stream));
+    return NGSLD_OK;
+  }
+
+  // ---- what consuming a batch is made of ----
+  // A likelihood matrix that flags more pairs than the host should replay, and this batch went out before the exact store was
+  // there: build it (once), replay the batch's pairs on the device -- in the records the arm reads, on the copy stream -- and
+  // send the flag head again.  `applied`: the batch's listed pairs are settled on the device, now or since its issue; where that
+  // is news (applied != slot_dev_applied[k]) the arm takes again what it had from the records before: text every row's
+  // length, records their copy.
+  int settle_late_on_device(int k, const Batch &b, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext, bool &applied) {
+    applied = c->slot_dev_applied[k];
+    if (applied || !exact_store_wanted(c, c->h_flags[k].p[0] - c->h_flags[k].p[1])) return NGSLD_OK;
+    RC_TRY(try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, d_std, d_ext, c->copy_stream, true, k, &applied,
+                                 exact_sites_needed(c, b.r0, b.r1)));
+    return !applied ? NGSLD_OK : send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], c->copy_stream, false);
+  }
+
+  bool batch_needs_host(int k, size_t bi) const {  // a value beyond the device formatter's fast path: the batch goes out as records
+    return (c->h_text_meta[k].p[1] & 0xffffffffull) != 0 || text_fallback_forced(bi);
+  }
+
   // recs' entries among what send_flag_rows wrote for the slot (the same list, the same bound as the kernel's): rep_s1 / rep_s2 /
   // hp_row filled; false when the batch left more pairs than the kernel writes, or one is not there
-  auto find_flag_rows = [&](int k, bool applied) -> bool {
+  bool find_flag_rows(int k, bool applied) {
     const uint32_t *hd = c->h_flags[k].p;
     const bool host_list = applied || hd[7] != 0;
     const uint32_t n = host_list ? hd[1] : hd[0];
@@ -622,13 +664,11 @@ static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sin
       rep_s2[j] = rows[at].s2;
     }
     return true;
-  };
+  }
+
   // the replayed records' value columns over the old ones in the text the host holds; false: a row has another length now (or
   // is not where it should be) -- the caller takes the device's way
-  uint64_t patch_fail_every = 0;  // tests: every n-th patched batch pretends its last row changed length (the fallback's way out)
-  if (const char *e = test_knob("TEXT_HOST_PATCH_FAIL_EVERY")) patch_fail_every = std::strtoull(e, nullptr, 10);
-  uint64_t patched_batches = 0;
-  auto apply_host_patch = [&](int k) -> bool {
+  bool apply_host_patch(int k) {
     const uint64_t total = c->h_text_meta[k].p[0];
     const bool pretend = patch_fail_every != 0 && ++patched_batches % patch_fail_every == 0;
     char *text_p = c->h_text[k].p;
@@ -649,13 +689,12 @@ static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sin
       std::memcpy(row + at, buf + 3, m - 3);
     }
     return true;
-  };
-  auto device_patch = [&](int k, const Batch &b, bool &rewrite) -> int {
+  }
+
+  int device_patch(int k, const Batch &b, bool &rewrite) {
     // flagged pairs: replayed on the host, patched into the device records, and the row lengths derived again --
     // all on the copy stream, beside the next batch's pair kernel
-    int rcr = replay_flagged(c, recs, c->h_row_off[b.r0], nullptr, nullptr, c->d_std[k].p, ext ? c->d_ext[k].p : nullptr,
-                           c->copy_stream, &rep_s1, &rep_s2);
-    if (rcr != NGSLD_OK) return rcr;
+    RC_TRY(replay_flagged(c, recs, c->h_row_off[b.r0], nullptr, nullptr, c->d_std[k].p, ext ? c->d_ext[k].p : nullptr, c->copy_stream, &rep_s1, &rep_s2));
     // Only the replayed rows' lengths are derived again (replay_flagged left their record indices in d_patch_idx); the
     // prefix sums are taken again only if one of them changed -- a full length pass + scan beside the next batch's pair
     // kernel cost that kernel ~1 ms of every 11 (profiles/r04/e2e_timeline.txt)
@@ -667,36 +706,36 @@ static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sin
       HIP_TRY(c, hipMemcpyAsync(c->d_patch_s2.p, rep_s2.data(), recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_stream));
       HIP_TRY(c, hipMemsetAsync(c->d_text_meta[k].p + 2, 0, sizeof(uint64_t), c->copy_stream));
       const TextArgs t = text_args(b, k);
-      HIP_TRY(c, launch_text_relength(t, c->d_patch_idx.p, c->d_patch_s1.p, c->d_patch_s2.p, recs.size(), c->d_text_meta[k].p + 2,
-                                      c->copy_stream));
-      HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                c->copy_stream));
+      HIP_TRY(c, launch_text_relength(t, c->d_patch_idx.p, c->d_patch_s1.p, c->d_patch_s2.p, recs.size(), c->d_text_meta[k].p + 2, c->copy_stream));
+      HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
       HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
       if (c->h_text_meta[k].p[2] != 0) {
         HIP_TRY(c, text_scan(c->d_scan_tmp2.p, scan_bytes, c->d_lens[k].p, c->d_offs[k].p, b.n, c->d_text_meta[k].p, c->copy_stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                  c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
         HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
       }
     }
     return NGSLD_OK;
-  };
-  auto finish_text = [&](int k, size_t bi, const Batch &b, bool &rewrite, bool &as_records, ngsld_batch &out, double &t_wr) -> int {
+  }
+
+  void fill_records(int k, const Batch &b, ngsld_batch &out) {  // the batch goes to the sink as records: the slot's host buffers
+    relative_items(c, b.r0, b.r1, rel_items, out);
+    out.std = c->h_std[k].p;
+    out.ext = ext ? c->h_ext[k].p : nullptr;
+  }
+
+  // the batch's text (or, for a batch the formatter gave up on, its records) onto the host and into `out`
+  int finish_text(int k, size_t bi, bool &rewrite, bool &as_records, ngsld_batch &out) {
+    const Batch &b = batches[bi];
     const uint64_t total = c->h_text_meta[k].p[0];
     if (batch_needs_host(k, bi)) {
       as_records = true;  // a value beyond the device formatter's fast path: this batch goes out as records
       HIP_TRY(c, c->h_std[k].resize(cap));
       if (ext) HIP_TRY(c, c->h_ext[k].resize(cap));
-      if (b.n) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_std[k].p, c->d_std[k].p, b.n * sizeof(ngsld_rec_std), hipMemcpyDeviceToHost,
-                                  c->copy_stream));
-        if (ext)
-          HIP_TRY(c, hipMemcpyAsync(c->h_ext[k].p, c->d_ext[k].p, b.n * sizeof(ngsld_rec_ext), hipMemcpyDeviceToHost,
-                                    c->copy_stream));
-      }
+      HIP_TRY(c, copy_records_to_host(c, k, c->d_std[k].p, c->d_ext[k].p, b.n, c->copy_stream));
       HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-      const int rc1 = need_host_items();
-      if (rc1 != NGSLD_OK) return rc1;
+      RC_TRY(ensure_host_items(c));
+      fill_records(k, b, out);
     } else {
       if (total > c->d_text[k].n) {
         HIP_TRY(c, c->d_text[k].resize(total + total / 8));
@@ -717,146 +756,137 @@ static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sin
       out.text_len = total;
     }
     return NGSLD_OK;
-  };
-  int rc = NGSLD_OK;
-  const bool trace = std::getenv("NGSLD_TRACE") != nullptr;  // dev: per-batch host timeline on stderr
+  }
+
+  // the batch's text: its length is known now; the rows are written and copied on the copy stream while the pair
+  // kernel of the next batch (already enqueued) runs on the compute stream
+  int consume_text(size_t bi, ngsld_batch &out) {
+    const int k = slot_of(bi);
+    const Batch &b = batches[bi];
+    HIP_TRY(c, hipEventSynchronize(c->ev_kernel_done[k]));
+    t_ev = now_ms();
+    bool as_records = false;
+    bool rewrite = false;     // the rows the issue wrote are stale: records were patched since
+    bool host_patch = false;  // the host's pairs go into the text the host holds (below)
+    if (replay) c->flagged_pairs += c->h_flags[k].p[0];
+    if (replay && c->h_flags[k].p[0] != 0) {
+      bool applied = false;
+      RC_TRY(settle_late_on_device(k, b, c->d_std[k].p, ext ? c->d_ext[k].p : nullptr, applied));
+      if (applied != c->slot_dev_applied[k]) {  // (settled just now: every row's length again)
+        HIP_TRY(c, hipMemsetAsync(c->d_text_meta[k].p, 0, 4 * sizeof(uint64_t), c->copy_stream));
+        const TextArgs t = text_args(b, k);
+        HIP_TRY(c, launch_text_lengths(t, c->copy_stream));
+        HIP_TRY(c, text_scan(c->d_scan_tmp2.p, scan_bytes, c->d_lens[k].p, c->d_offs[k].p, b.n, c->d_text_meta[k].p, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+        rewrite = true;
+      }
+      RC_TRY(flagged_records(c, c->h_flags[k].p, c->d_flags[k].p, c->flag_cap[k], b.n, recs, applied));
+      // The pairs left to the host (the headline's few dozen, a batch's host-only pairs behind a device-side replay): replayed
+      // on the host's threads and written over their rows' value columns in the text the host receives -- send_flag_rows told
+      // which pairs they are and where their rows lie, so NOTHING is submitted to the device here.  (Rounds 1-5 located them,
+      // patched the device's records, took the rows' lengths again and wrote the batch's text again -- kernels that, in a
+      // hardware queue shared with the compute streams, stood behind the pair kernels of the next two batches.)
+      host_patch = host_patch_on && !recs.empty() && !rewrite && applied == c->slot_dev_applied[k] && !batch_needs_host(k, bi) &&
+                   c->h_text_meta[k].p[3] == 0 && c->h_text_meta[k].p[0] <= c->d_text[k].n && find_flag_rows(k, applied);
+      if (host_patch) {
+        hp_std.resize(recs.size());
+        hp_ext.resize(ext ? recs.size() : 0);
+        RC_TRY(replay_pairs_on_host(c, rep_s1.data(), rep_s2.data(), recs.size(), hp_std.data(), ext ? hp_ext.data() : nullptr));
+      } else {
+        RC_TRY(device_patch(k, b, rewrite));
+      }
+    }
+    RC_TRY(finish_text(k, bi, rewrite, as_records, out));
+    if (host_patch) {
+      if (!as_records && apply_host_patch(k)) {
+        c->replayed_pairs += recs.size();
+        c->host_replayed_total += recs.size();
+        c->text_rows_patched += recs.size();
+      } else {  // (a replayed row of another length -- once in a few thousand replays: the device's way, the text copied again)
+        RC_TRY(device_patch(k, b, rewrite));
+        RC_TRY(finish_text(k, bi, rewrite, as_records, out));
+      }
+    }
+    return NGSLD_OK;
+  }
+
+  int consume_records(size_t bi, ngsld_batch &out) {
+    const int k = slot_of(bi);
+    const Batch &b = batches[bi];
+    HIP_TRY(c, hipEventSynchronize(direct ? c->ev_kernel_done[k] : c->ev_copy_done[k]));
+    if (trace) {
+      const uint32_t *hd = c->h_flags[k].p;
+      std::fprintf(stderr, "[trace] batch %zu (%llu pairs): issue next %.2f..%.2f, records on the host %.2f, flag head %u %u %u %u %u %u %u %u\n", bi,
+                   (unsigned long long)b.n, t_a, t_b, now_ms(), replay ? hd[0] : 0u, replay ? hd[1] : 0u, replay ? hd[2] : 0u, replay ? hd[3] : 0u,
+                   replay ? hd[4] : 0u, replay ? hd[5] : 0u, replay ? hd[6] : 0u, replay ? hd[7] : 0u);
+    }
+    if (replay) c->flagged_pairs += c->h_flags[k].p[0];
+    if (replay && c->h_flags[k].p[0] != 0) {  // flagged pairs: replayed on the host, patched into the batch's buffers
+      bool applied = false;
+      RC_TRY(settle_late_on_device(k, b, dev_std[k], dev_ext[k], applied));
+      if (applied != c->slot_dev_applied[k]) {  // (settled just now; the records had been copied already: once more)
+        if (!direct) HIP_TRY(c, copy_records_to_host(c, k, c->d_std[k].p, c->d_ext[k].p, b.n, c->copy_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+      }
+      RC_TRY(flagged_records(c, c->h_flags[k].p, c->d_flags[k].p, c->flag_cap[k], b.n, recs, applied));
+      RC_TRY(replay_flagged(c, recs, c->h_row_off[b.r0], c->h_std[k].p, ext ? c->h_ext[k].p : nullptr, nullptr, nullptr, nullptr));
+    }
+    fill_records(k, b, out);
+    return NGSLD_OK;
+  }
+
   // S - 1 batches are in flight while one is consumed: the slot of batch bi + S - 1 was last used by batch bi - 1, whose
   // sink call has returned
-  for (size_t bi = 0; rc == NGSLD_OK && bi + 1 < (size_t)S && bi < batches.size(); ++bi) rc = issue(bi);
-  for (size_t bi = 0; rc == NGSLD_OK && bi < batches.size(); ++bi) {
-    const int k = (int)(bi % (size_t)S);
-    const double t_a = now_ms();
-    if (bi + (size_t)S - 1 < batches.size()) {
-      rc = issue(bi + (size_t)S - 1);
+  int run() {
+    int rc = NGSLD_OK;
+    for (size_t bi = 0; rc == NGSLD_OK && bi + 1 < (size_t)S && bi < batches.size(); ++bi) rc = issue(bi);
+    for (size_t bi = 0; rc == NGSLD_OK && bi < batches.size(); ++bi) {
+      t_ev = t_wr = 0.0;
+      t_a = now_ms();
+      if (bi + (size_t)S - 1 < batches.size()) {
+        rc = issue(bi + (size_t)S - 1);
+        if (rc != NGSLD_OK) break;
+      }
+      t_b = now_ms();
+      const Batch &b = batches[bi];
+      ngsld_batch out{};
+      out.s1_begin = b.r0;
+      out.s1_end = b.r1;
+      out.n_pairs = b.n;
+      Range range_wait(text ? "ngsld:consume batch (text rows, D2H, replay, sink)" : "ngsld:consume batch (wait for records, replay, sink)");
+      rc = text ? consume_text(bi, out) : consume_records(bi, out);
       if (rc != NGSLD_OK) break;
+      if (trace)
+        std::fprintf(stderr, "[trace] batch %zu: issue next %.2f..%.2f, its kernels done %.2f, text written + on the host %.2f, replay done %.2f\n",
+                     bi, t_a, t_b, t_ev, t_wr, now_ms());
+      Range range_sink("ngsld:sink");
+      if (sink(user, &out) != 0) rc = fail(c, NGSLD_ERR_SINK, "sink callback failed");
     }
-    const double t_b = now_ms();
-    const Batch &b = batches[bi];
-    const uint64_t i0 = c->h_item_off[b.r0], i1 = c->h_item_off[b.r1];
-    ngsld_batch out{};
-    out.s1_begin = b.r0;
-    out.s1_end = b.r1;
-    out.n_pairs = b.n;
-    bool as_records = !text;
-    Range range_wait(text ? "ngsld:consume batch (text rows, D2H, replay, sink)" : "ngsld:consume batch (wait for records, replay, sink)");
-    double t_ev = 0.0, t_wr = 0.0;
-    if (text) {
-      // the batch's text: its length is known now; the rows are written and copied on the copy stream while the pair
-      // kernel of the next batch (already enqueued) runs on the compute stream
-      HIP_TRY(c, hipEventSynchronize(c->ev_kernel_done[k]));
-      t_ev = now_ms();
-      bool rewrite = false;  // the rows the issue wrote are stale: records were patched since
-      bool host_patch = false;  // the host's pairs go into the text the host holds (below)
-      if (replay) c->flagged_pairs += c->h_flags[k].p[0];
-      if (replay && c->h_flags[k].p[0] != 0) {
-        bool applied = c->slot_dev_applied[k];
-        if (!applied && exact_store_wanted(c, c->h_flags[k].p[0] - c->h_flags[k].p[1])) {
-          // a likelihood matrix that flags more pairs than the host should replay, and this batch went out before the exact
-          // store was there: build it (once), replay the batch's pairs on the device, take every row's length again
-          int rcx = try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, c->d_std[k].p,
-                                          ext ? c->d_ext[k].p : nullptr, c->copy_stream, true, k, &applied, exact_sites_needed(c, b.r0, b.r1));
-          if (rcx != NGSLD_OK) return rcx;
-          if (applied) {
-            rcx = send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], c->copy_stream, false);
-            if (rcx != NGSLD_OK) return rcx;
-            HIP_TRY(c, hipMemsetAsync(c->d_text_meta[k].p, 0, 4 * sizeof(uint64_t), c->copy_stream));
-            const TextArgs t = text_args(b, k);
-            HIP_TRY(c, launch_text_lengths(t, c->copy_stream));
-            HIP_TRY(c, text_scan(c->d_scan_tmp2.p, scan_bytes, c->d_lens[k].p, c->d_offs[k].p, b.n, c->d_text_meta[k].p, c->copy_stream));
-            HIP_TRY(c, hipMemcpyAsync(c->h_text_meta[k].p, c->d_text_meta[k].p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->copy_stream));
-            HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-            rewrite = true;
-          }
-        }
-        int rcr = flagged_records(c, c->h_flags[k].p, c->d_flags[k].p, c->flag_cap[k], b.n, recs, applied);
-        if (rcr != NGSLD_OK) return rcr;
-        // The pairs left to the host (the headline's few dozen, a batch's host-only pairs behind a device-side replay): replayed
-        // on the host's threads and written over their rows' value columns in the text the host receives -- send_flag_rows told
-        // which pairs they are and where their rows lie, so NOTHING is submitted to the device here.  (Rounds 1-5 located them,
-        // patched the device's records, took the rows' lengths again and wrote the batch's text again -- kernels that, in a
-        // hardware queue shared with the compute streams, stood behind the pair kernels of the next two batches.)
-        host_patch = host_patch_on && !recs.empty() && !rewrite && applied == c->slot_dev_applied[k] && !batch_needs_host(k, bi) &&
-                     c->h_text_meta[k].p[3] == 0 && c->h_text_meta[k].p[0] <= c->d_text[k].n && find_flag_rows(k, applied);
-        if (host_patch) {
-          hp_std.resize(recs.size());
-          hp_ext.resize(ext ? recs.size() : 0);
-          rcr = replay_pairs_on_host(c, rep_s1.data(), rep_s2.data(), recs.size(), hp_std.data(), ext ? hp_ext.data() : nullptr);
-        } else {
-          rcr = device_patch(k, b, rewrite);
-        }
-        if (rcr != NGSLD_OK) return rcr;
-      }
-      int rcf = finish_text(k, bi, b, rewrite, as_records, out, t_wr);
-      if (rcf != NGSLD_OK) return rcf;
-      if (host_patch) {
-        if (!as_records && apply_host_patch(k)) {
-          c->replayed_pairs += recs.size();
-          c->host_replayed_total += recs.size();
-          c->text_rows_patched += recs.size();
-        } else {  // (a replayed row of another length -- once in a few thousand replays: the device's way, the text copied again)
-          rcf = device_patch(k, b, rewrite);
-          if (rcf == NGSLD_OK) rcf = finish_text(k, bi, b, rewrite, as_records, out, t_wr);
-          if (rcf != NGSLD_OK) return rcf;
-        }
-      }
-    } else {
-      HIP_TRY(c, hipEventSynchronize(direct ? c->ev_kernel_done[k] : c->ev_copy_done[k]));
-      if (trace) {
-        const uint32_t *hd = c->h_flags[k].p;
-        std::fprintf(stderr, "[trace] batch %zu (%llu pairs): issue next %.2f..%.2f, records on the host %.2f, flag head %u %u %u %u %u %u %u %u\n", bi,
-                     (unsigned long long)b.n, t_a, t_b, now_ms(), replay ? hd[0] : 0u, replay ? hd[1] : 0u, replay ? hd[2] : 0u, replay ? hd[3] : 0u,
-                     replay ? hd[4] : 0u, replay ? hd[5] : 0u, replay ? hd[6] : 0u, replay ? hd[7] : 0u);
-      }
-      if (replay) c->flagged_pairs += c->h_flags[k].p[0];
-      if (replay && c->h_flags[k].p[0] != 0) {  // flagged pairs: replayed on the host, patched into the batch's buffers
-        bool applied = c->slot_dev_applied[k];
-        if (!applied && exact_store_wanted(c, c->h_flags[k].p[0] - c->h_flags[k].p[1])) {  // (see the text branch above)
-          int rcx = try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k],
-                                          c->copy_stream, true, k, &applied, exact_sites_needed(c, b.r0, b.r1));
-          if (rcx != NGSLD_OK) return rcx;
-          if (applied) {
-            rcx = send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], c->copy_stream, false);
-            if (rcx != NGSLD_OK) return rcx;
-            if (!direct && b.n) {  // (the records had been copied already: once more)
-              HIP_TRY(c, hipMemcpyAsync(c->h_std[k].p, c->d_std[k].p, b.n * sizeof(ngsld_rec_std), hipMemcpyDeviceToHost, c->copy_stream));
-              if (ext)
-                HIP_TRY(c, hipMemcpyAsync(c->h_ext[k].p, c->d_ext[k].p, b.n * sizeof(ngsld_rec_ext), hipMemcpyDeviceToHost, c->copy_stream));
-            }
-            HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-          }
-        }
-        int rcr = flagged_records(c, c->h_flags[k].p, c->d_flags[k].p, c->flag_cap[k], b.n, recs, applied);
-        if (rcr == NGSLD_OK)
-          rcr = replay_flagged(c, recs, c->h_row_off[b.r0], c->h_std[k].p, ext ? c->h_ext[k].p : nullptr, nullptr, nullptr, nullptr);
-        if (rcr != NGSLD_OK) return rcr;
-      }
-    }
-    if (as_records) {
-      rel_items.assign(c->h_items.begin() + (ptrdiff_t)i0, c->h_items.begin() + (ptrdiff_t)i1);
-      for (auto &it : rel_items) it.first_record -= c->h_row_off[b.r0];
-      out.n_items = i1 - i0;
-      out.items = rel_items.data();
-      out.std = c->h_std[k].p;
-      out.ext = ext ? c->h_ext[k].p : nullptr;
-    }
-    if (trace)
-      std::fprintf(stderr, "[trace] batch %zu: issue next %.2f..%.2f, its kernels done %.2f, text written + on the host %.2f, replay done %.2f\n",
-                   bi, t_a, t_b, t_ev, t_wr, now_ms());
-    Range range_sink("ngsld:sink");
-    if (sink(user, &out) != 0) rc = fail(c, NGSLD_ERR_SINK, "sink callback failed");
+    return drain(c, rc, {c->stream, c->stream2, c->text_stream, c->copy_stream});
   }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  if (c->text_stream) HIP_TRY(c, hipStreamSynchronize(c->text_stream));
-  HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-  if (rc != NGSLD_OK) return rc;
-  if (c->exact_state.load() == 1) {  // (the store's builder is still at the sites behind this run's rows: its errors are this run's)
-    bool have = false;
-    const int rcs = wait_exact_store(c, c->n_sites, &have);
-    if (rcs != NGSLD_OK) return rcs;
-  }
-  return check_status(c);
+};
+
+static int run_range(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn sink, void *user) {
+  c->ev_used = 0;
+  c->timed_stream = c->stream;
+  c->timed_pairs = c->h_row_off[s1_end] - c->h_row_off[s1_begin];
+  c->replayed_pairs = 0;
+  c->replayed_on_device = 0;
+  c->flagged_pairs = 0;
+  c->text_rows_patched = 0;
+  if (c->reserve_thread.joinable()) c->reserve_thread.join();  // (ngsld_reserve_text_buffers: h_text[] is this thread's again)
+  bool text = c->text_mode;
+  if (text) RC_TRY(upload_text_prefix(c, &text));
+  if (!text) RC_TRY(ensure_host_items(c));  // (record batches carry their items to the sink; text batches need none -- the replay finds its pairs on the device)
+  BatchRun run(c, s1_begin, s1_end, sink, user, text);
+  int rc = run.plan_batches();
+  if (rc == NGSLD_OK) rc = run.build_runs();
+  if (rc == NGSLD_OK) rc = run.reserve_slots();
+  if (rc == NGSLD_OK) rc = run.run();
+  return rc == NGSLD_OK ? finish_run(c) : rc;
 }
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Text output of a likelihood matrix that is NOT SNP-called (degenerate sites were found at ngsld_set_geno_*): a third of the
@@ -916,26 +946,9 @@ static int group_text_kernels(ngsld_ctx *c, const ReadyRecords &rr, const std::v
   HIP_TRY(c, hipMemcpyAsync(c->d_group_first.p, first.data(), (nb + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(c->d_group_needs.p, 0, (nb + 1) * sizeof(int), st));
   HIP_TRY(c, hipMemsetAsync(c->d_group_meta.p, 0, 4 * sizeof(uint64_t), st));
-  auto args = [&](const TextBatch &b, uint32_t j) -> TextArgs {
-    TextArgs t{};
-    t.items = c->d_items.p + c->h_item_off[b.r0];
-    t.n_items = c->h_item_off[b.r1] - c->h_item_off[b.r0];
-    t.out_base = c->h_row_off[b.r0];
-    t.n_pairs = b.n;
-    t.std_rec = rr.std + b.rec0;
-    t.ext_rec = ext ? rr.ext + b.rec0 : nullptr;
-    t.maf = c->d_maf.p;
-    t.cum = c->d_cum.p;
-    t.infc = c->d_infc.p;
-    t.labels = c->have_labels ? c->d_labels.p : nullptr;
-    t.label_off = c->d_label_off.p;
-    t.lens = c->d_group_lens.p + b.rec0;
-    t.offs = c->d_group_offs.p + b.rec0;   // (prefix sums over the GROUP: offsets into the group's text)
-    t.text = c->d_group_text.p;
-    t.text_cap = 0;
-    t.overflow = c->d_group_meta.p + 3;
-    t.needs_host = c->d_group_needs.p + j;
-    return t;
+  auto args = [&](const TextBatch &b, uint32_t j) -> TextArgs {  // (prefix sums over the GROUP: offsets into the group's text)
+    return make_text_args(c, b.r0, b.r1, b.n, rr.std + b.rec0, ext ? rr.ext + b.rec0 : nullptr, c->d_group_lens.p + b.rec0, c->d_group_offs.p + b.rec0,
+                          c->d_group_text.p, c->d_group_needs.p + j, c->d_group_meta.p + 3);
   };
   for (uint32_t j = 0; j < nb; ++j) HIP_TRY(c, launch_text_lengths(args(tb[j], j), st));
   HIP_TRY(c, text_scan(c->d_scan_tmp.p, scan_bytes, c->d_group_lens.p, c->d_group_offs.p, n_group, c->d_group_meta.p, st));
@@ -964,29 +977,21 @@ static int group_text_kernels(ngsld_ctx *c, const ReadyRecords &rr, const std::v
 static int group_text_to_sink(ngsld_ctx *c, const ReadyRecords &rr, const std::vector<TextBatch> &tb, ngsld_sink_fn sink, void *user) {
   const bool ext = c->params.extend_out != 0;
   const size_t nb = tb.size();
-  HIP_TRY(c, hipEventSynchronize(c->ev_kernel_done[0]));  // T(g) is through: bounds and fallbacks are in host memory
+  int rc = NGSLD_OK;
+  // T(g) is through: bounds and fallbacks are in host memory
+  if (const hipError_t e = hipEventSynchronize(c->ev_kernel_done[0]); e != hipSuccess) rc = hip_fail(c, e, "hipEventSynchronize(c->ev_kernel_done[0])");
   const uint64_t *bounds = c->h_group_bounds.p;
   const int *needs = c->h_group_needs.p;
   constexpr int S = ngsld_ctx::kSlots;
   std::vector<Item> rel_items;
-  auto fallback = [&](size_t j) {
-    bool f = needs[j] != 0;
-    if (const char *e = test_knob("TEXT_FALLBACK_EVERY")) {  // tests: every n-th batch takes the record path
-      const uint64_t every = std::strtoull(e, nullptr, 10);
-      if (every > 0 && j % every == every - 1) f = true;
-    }
-    return f;
-  };
+  auto fallback = [&](size_t j) { return needs[j] != 0 || text_fallback_forced(j); };
   auto issue_copy = [&](size_t j) -> int {
     const int k = (int)(j % (size_t)S);
     const TextBatch &b = tb[j];
     if (fallback(j)) {
       HIP_TRY(c, c->h_std[k].resize(b.n ? b.n : 1));
       if (ext) HIP_TRY(c, c->h_ext[k].resize(b.n ? b.n : 1));
-      if (b.n) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_std[k].p, rr.std + b.rec0, b.n * sizeof(ngsld_rec_std), hipMemcpyDeviceToHost, c->copy_stream));
-        if (ext) HIP_TRY(c, hipMemcpyAsync(c->h_ext[k].p, rr.ext + b.rec0, b.n * sizeof(ngsld_rec_ext), hipMemcpyDeviceToHost, c->copy_stream));
-      }
+      HIP_TRY(c, copy_records_to_host(c, k, rr.std + b.rec0, ext ? rr.ext + b.rec0 : nullptr, b.n, c->copy_stream));
     } else {
       const uint64_t len = bounds[j + 1] - bounds[j];
       if (len > c->h_text[k].n) HIP_TRY(c, c->h_text[k].resize(len + len / 8));
@@ -995,14 +1000,8 @@ static int group_text_to_sink(ngsld_ctx *c, const ReadyRecords &rr, const std::v
     HIP_TRY(c, hipEventRecord(c->ev_copy_done[k], c->copy_stream));
     return NGSLD_OK;
   };
-  int rc = NGSLD_OK;
-  for (size_t j = 0; rc == NGSLD_OK && j + 1 < (size_t)S && j < nb; ++j) rc = issue_copy(j);
-  for (size_t j = 0; rc == NGSLD_OK && j < nb; ++j) {
+  auto deliver = [&](size_t j) -> int {
     const int k = (int)(j % (size_t)S);
-    if (j + (size_t)S - 1 < nb) {
-      rc = issue_copy(j + (size_t)S - 1);
-      if (rc != NGSLD_OK) break;
-    }
     const TextBatch &b = tb[j];
     Range range_wait("ngsld:consume batch (text of a group, D2H, sink)");
     HIP_TRY(c, hipEventSynchronize(c->ev_copy_done[k]));
@@ -1011,13 +1010,8 @@ static int group_text_to_sink(ngsld_ctx *c, const ReadyRecords &rr, const std::v
     out.s1_end = b.r1;
     out.n_pairs = b.n;
     if (fallback(j)) {
-      const int rci = ensure_host_items(c);
-      if (rci != NGSLD_OK) return rci;
-      const uint64_t i0 = c->h_item_off[b.r0], i1 = c->h_item_off[b.r1];
-      rel_items.assign(c->h_items.begin() + (ptrdiff_t)i0, c->h_items.begin() + (ptrdiff_t)i1);
-      for (auto &it : rel_items) it.first_record -= c->h_row_off[b.r0];
-      out.n_items = i1 - i0;
-      out.items = rel_items.data();
+      RC_TRY(ensure_host_items(c));
+      relative_items(c, b.r0, b.r1, rel_items, out);
       out.std = c->h_std[k].p;
       out.ext = ext ? c->h_ext[k].p : nullptr;
     } else {
@@ -1025,10 +1019,14 @@ static int group_text_to_sink(ngsld_ctx *c, const ReadyRecords &rr, const std::v
       out.text_len = bounds[j + 1] - bounds[j];
     }
     Range range_sink("ngsld:sink");
-    if (sink(user, &out) != 0) rc = fail(c, NGSLD_ERR_SINK, "sink callback failed");
+    return sink(user, &out) != 0 ? fail(c, NGSLD_ERR_SINK, "sink callback failed") : NGSLD_OK;
+  };
+  for (size_t j = 0; rc == NGSLD_OK && j + 1 < (size_t)S && j < nb; ++j) rc = issue_copy(j);
+  for (size_t j = 0; rc == NGSLD_OK && j < nb; ++j) {
+    if (j + (size_t)S - 1 < nb) rc = issue_copy(j + (size_t)S - 1);
+    if (rc == NGSLD_OK) rc = deliver(j);
   }
-  HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-  return rc;
+  return drain(c, rc, {c->copy_stream});
 }
 
 static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn sink, void *user, uint64_t group_pairs) {
@@ -1041,8 +1039,7 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
   for (uint64_t r0 = s1_begin; r0 < s1_end;) {
     // (the first group a quarter of the size: nothing overlaps its kernels, the sink waits for them)
     const uint64_t target = groups.empty() ? std::max<uint64_t>(group_pairs / 4, std::min<uint64_t>(group_pairs, 1ull << 22)) : group_pairs;
-    uint64_t r1 = r0 + 1;
-    while (r1 < s1_end && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= target) ++r1;
+    const uint64_t r1 = rows_within(c->h_row_off, r0, s1_end, target);
     groups.push_back({r0, r1, c->h_row_off[r1] - c->h_row_off[r0]});
     cap = std::max(cap, groups.back().n);
     r0 = r1;
@@ -1069,8 +1066,7 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
     HIP_TRY(c, c->d_group_text.resize(cap * row_guess));
     const size_t scan_bytes = text_scan_temp_bytes(cap);
     HIP_TRY(c, c->d_scan_tmp.resize(scan_bytes ? scan_bytes : 1));
-    const int rcr = reserve_device_run(c, cap);
-    if (rcr != NGSLD_OK) return rcr;
+    RC_TRY(reserve_device_run(c, cap));
   }
   if (c->reserve_thread.joinable()) c->reserve_thread.join();  // (ngsld_reserve_text_buffers: h_text[] is this thread's again)
   struct FlagText {  // (ngsld_run_device's launches flag what text needs flagged while this run lasts)
@@ -1101,8 +1097,7 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
     const ReadyRecords ready{c->d_group_std[k].p, ext ? c->d_group_ext[k].p : nullptr, c->h_row_off[groups[g].r0]};
     tb.clear();
     for (uint64_t r0 = groups[g].r0; r0 < groups[g].r1;) {
-      uint64_t r1 = r0 + 1;
-      while (r1 < groups[g].r1 && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= text_batch) ++r1;
+      const uint64_t r1 = rows_within(c->h_row_off, r0, groups[g].r1, text_batch);
       tb.push_back({r0, r1, c->h_row_off[r1] - c->h_row_off[r0], c->h_row_off[r0] - ready.base});
       r0 = r1;
     }
@@ -1127,132 +1122,7 @@ static int run_grouped(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_s
   c->replayed_pairs = replayed;
   c->replayed_on_device = on_device;
   c->timed_pairs = c->h_row_off[s1_end] - c->h_row_off[s1_begin];
-  if (c->exact_state.load() == 1) {
-    bool have = false;
-    const int rcs = wait_exact_store(c, c->n_sites, &have);
-    if (rcs != NGSLD_OK) return rcs;
-  }
-  return check_status(c);
-}
-
-// ---- the host frame of the record passes (record_pass.h) ----
-void SiteFilter::prepare(const ngsld_ctx *c, const double *min_maf) {
-  exact_gaps = dist_prefix(c, cum, infc);
-  if (min_maf == nullptr) return;
-  maf_ok.resize(c->n_sites);
-  for (uint64_t s = 0; s < c->n_sites; ++s) {
-    const double m = c->h_maf[s];
-    maf_ok[s] = (m - m == 0.0 && ngsld::prune_printed(m) >= *min_maf) ? 1 : 0;  // (a NaN maf never passes, as in R)
-  }
-}
-
-int SiteFilter::check_limit(ngsld_ctx *c, const char *pass, double limit) const {
-  if (!exact_gaps && std::isfinite(limit)) return fail(c, NGSLD_ERR_UNSUPPORTED, std::string(pass) + " max_kb_dist needs integer position gaps");
-  return NGSLD_OK;
-}
-
-int SiteFilter::upload(ngsld_ctx *c) {
-  const uint64_t n = c->n_sites;
-  HIP_TRY(c, d_cum.resize(n));
-  HIP_TRY(c, d_infc.resize(n));
-  HIP_TRY(c, hipMemcpy(d_cum.p, cum.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_infc.p, infc.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (maf_ok.empty()) return NGSLD_OK;
-  HIP_TRY(c, d_maf_ok.resize(n));
-  HIP_TRY(c, hipMemcpy(d_maf_ok.p, maf_ok.data(), n, hipMemcpyHostToDevice));
-  return NGSLD_OK;
-}
-
-int RecordPass::open(ngsld_ctx *ctx, uint64_t chunk, const uint8_t *only_rows, bool fit_longest_row, bool with_ext) {
-  c = ctx;
-  chunk_pairs = chunk;
-  rows = only_rows;
-  uint64_t cap = chunk;
-  if (fit_longest_row) {
-    uint64_t pairs = 0, longest = 0;
-    for (uint64_t s = 0; s < c->n_sites; ++s)
-      if (rows == nullptr || rows[s]) {
-        pairs += c->h_row_off[s + 1] - c->h_row_off[s];
-        longest = std::max<uint64_t>(longest, c->h_row_off[s + 1] - c->h_row_off[s]);
-      }
-    cap = std::max<uint64_t>(std::min<uint64_t>(pairs, chunk), longest);
-  }
-  HIP_TRY(c, d_rec.resize(cap));
-  if (with_ext) HIP_TRY(c, d_ext.resize(cap));
-  HIP_TRY(c, ev.create());
-  return NGSLD_OK;
-}
-
-int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const Step &before, const Launch &launch, const Step &after) {
-  const uint64_t n = c->n_sites;
-  // The records are read as printed (ld_prune.h): the launches flag, and the replay settles, the pairs whose sixth decimal
-  // or sign rounding noise could change, as for text output -- a D one ulp off an odd / 128 tie would quantise to the other
-  // neighbour than the reference's "%f"
-  struct FlagText {
-    ngsld_ctx *c;
-    ~FlagText() { c->dev_run_flag_text = false; }
-  } flag_text{c};
-  c->dev_run_flag_text = true;
-  for (uint64_t r0 = 0; r0 < n;) {
-    if (rows != nullptr && !rows[r0]) {
-      ++r0;
-      continue;
-    }
-    uint64_t r1 = r0 + 1;  // (a chunk ends at a row that is not run)
-    while (r1 < n && (rows == nullptr || rows[r1]) && c->h_row_off[r1 + 1] - c->h_row_off[r0] <= chunk_pairs) ++r1;
-    const RecordChunk ch{r0, r1, c->h_row_off[r1] - c->h_row_off[r0], c->h_row_off[r0]};
-    if (ch.pairs > d_rec.n) return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(ch.pairs) + " pairs does not fit the record buffer");
-    if (ch.pairs > 0) {
-      const auto t0 = std::chrono::steady_clock::now();
-      int rc = ngsld_run_device(c, r0, r1, d_rec.p, d_ext.p, nullptr);  // (the ctx's stream: records final, replay done)
-      if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
-      if (rc != NGSLD_OK) return rc;
-      if (pairs_ms) *pairs_ms += ms_since(t0);
-      if (before) {
-        rc = before(ch);
-        if (rc != NGSLD_OK) return rc;
-      }
-      const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
-      const uint64_t max_items = record_slice_items();
-      HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-      for (uint64_t off = i0; off < i1; off += max_items) {
-        launch(ch, c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));
-        HIP_TRY(c, hipGetLastError());
-      }
-      HIP_TRY(c, hipEventRecord(ev.b, c->stream));
-      HIP_TRY(c, hipEventSynchronize(ev.b));
-      HIP_TRY(c, ev.add_elapsed(kernel_ms));
-      if (chunks) ++*chunks;
-      if (after) {
-        rc = after(ch);
-        if (rc != NGSLD_OK) return rc;
-      }
-    }
-    r0 = r1;
-  }
-  return NGSLD_OK;
-}
-
-int fail_value_range(ngsld_ctx *c, const char *pass, unsigned long long meta0) {
-  const unsigned long long k = meta0 - 1;
-  return fail(c, NGSLD_ERR_UNSUPPORTED, std::string("a ") + pass + " value of the pair of sites " + std::to_string(k >> 32) + " - " +
-                                            std::to_string(k & 0xffffffffull) + " reaches 2^38 micro-units (|x| >= 274877.906944)");
-}
-
-LabelPos label_pos(const char *label) {
-  const char *t = std::strchr(label, '\t');
-  LabelPos L{t ? std::string(label, t) : std::string(label), 0};
-  L.colon = L.key.find(':');
-  return L;
-}
-
-bool LabelPos::position(uint64_t *pos) const {
-  const char *num = colon == std::string::npos ? "" : key.c_str() + colon + 1;
-  const size_t len = std::strlen(num);
-  bool digits = len > 0 && len <= 19;
-  for (const char *q = num; *q; ++q) digits = digits && *q >= '0' && *q <= '9';
-  if (digits) *pos = std::strtoull(num, nullptr, 10);
-  return digits;
+  return finish_run(c);
 }
 }  // namespace eng
 }  // namespace ngsld
@@ -1266,10 +1136,7 @@ int ngsld_run(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn si
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // (a failure some earlier call already reported must not surface as a launch's "last error")
   Range range_("ngsld:run");
-  {
-    const int rcp = finish_device_run(c);  // (see ngsld_run_device)
-    if (rcp != NGSLD_OK) return rcp;
-  }
+  RC_TRY(finish_device_run(c));  // (see ngsld_run_device)
   StoreGuard store_guard{c};
   // Groups (run_grouped) where the matrix is known to be un-called -- one site in 64 or more is degenerate --, the device can
   // replay its pairs, the rows become text on the device and there are at least four text batches' worth of them; the groups'
@@ -1282,10 +1149,7 @@ int ngsld_run(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn si
     // The store first -- the matrix is known to be un-called, so it is wanted, and its builder can work beside the first group's
     // kernels -- and then the groups' buffers out of what is left: under a memory cap (ngsld_set_memory_budget) the store must not
     // lose its room to them.  Without the lanes' individual-major copy a group has nothing over a batch: batch by batch then.
-    if (!exact_store_started(c) && !c->exact_failed) {
-      const int rcs = start_exact_store(c);
-      if (rcs != NGSLD_OK) return rcs;
-    }
+    if (!exact_store_started(c) && !c->exact_failed) RC_TRY(start_exact_store(c));
     grouped = !c->exact_failed && c->xT_ready.load();
   }
   if (grouped) {
@@ -1296,8 +1160,7 @@ int ngsld_run(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn si
     grouped = test_knob("TEXT_GROUP_PAIRS") != nullptr || room_for(std::min(group_pairs, n_pairs) * per_pair, 4ull << 30, 512ull << 20);
     if (grouped) {  // (text on the device needs exact prefix sums of the gaps -- made here, once, for all the groups; where they cannot
                     // be had run_range sends records to the host formatter: that path stays whole)
-      const int rct = upload_text_prefix(c, &grouped);
-      if (rct != NGSLD_OK) return rct;
+      RC_TRY(upload_text_prefix(c, &grouped));
     }
     if (grouped) return run_grouped(c, s1_begin, s1_end, sink, user, group_pairs);
   }
@@ -1324,3 +1187,4 @@ int ngsld_last_kernel_time(ngsld_ctx *c, double *total_ms, uint64_t *n_launches,
 }
 
 }  // extern "C"
+

@@ -3,7 +3,7 @@
 // by chunk and run a kernel of their own over each chunk's items (ld_records.h).  What they share on the host is here, once: the
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
 // linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ.
-// Host code; the definitions are in engine_run.hip.
+// Host code; the definitions are in record_pass.hip.
 #pragma once
 
 #include "engine.h"
