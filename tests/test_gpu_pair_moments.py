@@ -8,7 +8,8 @@ individuals and the K chunks (np = 512, 192, 320, 576), sites whose alleles the 
 beside sites that do (a non-finite dosage must stay in its own row and column of the product), items with dropped candidates
 (the map from tile element to record), row ends inside tiles, and the rule the suite holds bit for bit: a pair's two sums do not
 depend on the tile, launch cut, batch or grid that computed them.  Bars: tests/util.py -- nIter and sample_size exact, values
-to 1e-9, degenerate pairs bit for bit."""
+to 1e-9, degenerate pairs bit for bit.
+Where 1e-9 cannot see, the pass's two sums are held by tests/test_gpu_pearson_exact.py (bits) and tests/test_gpu_pearson_margin.py."""
 import contextlib
 import os
 
