@@ -3,7 +3,8 @@
 //   engine.hip         contexts, the genotype matrix (upload + per-site prep), small queries
 //   engine_plan.hip    the pair-space plan: the s2 walk of calc_pair_LD for every s1 (ngsLD.cpp:240-282), items, runs
 //   engine_run.hip     ngsld_run / ngsld_run_device: batches, pair-kernel launches, device-side TSV
-//   engine_replay.hip  exact-order replay: flag lists, host threads, the device-side replays, the exact-value store
+//   engine_replay.hip  exact-order replay: flag lists, host threads, the device-side replays
+//   exact_store.hip    the exact-value store of the likelihood replay and the thread that builds it (exact_store.h)
 //   record_pass.hip    the host frame of the record passes (record_pass.h)
 #pragma once
 
@@ -247,6 +248,8 @@ class ReplayPool {
 using namespace ngsld;       // (an internal header: only the engine_*.hip units include it)
 using namespace ngsld::eng;
 
+#include "exact_store.h"
+
 // One pair a text batch leaves to the host's exact-order replay, written by the device right behind the batch's row lengths
 // (engine_replay.hip: flag_rows_to_host_kernel): with it the host replays the pair and overwrites the row's value columns in
 // the text it has received -- nothing goes back to the device, no kernel is submitted when the batch is consumed.
@@ -383,43 +386,26 @@ struct ngsld_ctx {
   bool replay_device = true;                       // flagged pairs replayed on the device where that is possible: called genotypes (ld_replay.hip), likelihoods (ld_replay_lkl.hip); NGSLD_REPLAY_DEVICE=0: host
   uint64_t replayed_on_device = 0;
   uint64_t text_rows_patched = 0;                  // rows of host-replayed pairs overwritten in the host's copy of a batch's text (last run)
-  // The exact store of the device-side replay of LIKELIHOOD matrices (ld_replay_lkl.hip): normal-space likelihoods and est_maf
-  // as the reference holds them when calc_pair_LD runs -- the HOST's libm, the sequential est_maf -- laid out like the planes.
-  // Input that came through ngsld_set_geno_lkl is such a store already (the planes are the caller's values), and so are the
-  // planes when no replay source is registered (the replay then runs on the device's own values, as the host's did); with a
-  // source it is built by the replay threads from the caller's raw values, the first time a run flags more pairs than the host
-  // should replay (exact_store_wanted), and kept until the matrix or its source changes.
-  DevBuf<double> d_xplanes, d_xmaf;
-  DevBuf<double> d_xT;                 // the store once more, individual-major, for the lane-per-pair kernel (ld_replay_lkl.hip)
-  std::atomic<bool> xT_ready{false};
-  DevBuf<uint32_t> d_xperm;            // ... where each site stands in it (rare sites first: ReplayLklArgs::xperm)
-  DevBuf<uint32_t> d_xdepth;              // ... and how small its sites' likelihoods get (ReplayLklArgs::xdepth)
+  ExactStore store;  // of the device-side replay of LIKELIHOOD matrices (exact_store.h); here: the policy and counters that outlive a store, the launches' scratch
+  int exact_mode = 1;                  // NGSLD_EXACT_STORE / ngsld_set_exact_store: 0 never (host replay only), 1 when it pays (default), 2 at the first flagged pair
   struct LaneScratch {   // what the lane-per-pair replay of one launch needs: the located pairs and their sorted order
     DevBuf<ReplayEntry> list;
     DevBuf<uint64_t> keys_a, keys_b;
     DevBuf<uint32_t> vals_a, vals_b;
     DevBuf<char> temp;
+    size_t temp_bytes = 0;             // the sort's own space, as last reserved
     void release() { list.release(); keys_a.release(); keys_b.release(); vals_a.release(); vals_b.release(); temp.release(); }
+    // all of it for a list of list_cap pairs; false: the device has no room -- everything is released, the HIP error cleared
+    bool reserve(uint64_t list_cap, uint64_t n_sites) {
+      temp_bytes = replay_sort_temp_bytes(list_cap, (uint32_t)n_sites);
+      if (list.resize(list_cap) == hipSuccess && keys_a.resize(list_cap) == hipSuccess && keys_b.resize(list_cap) == hipSuccess &&
+          vals_a.resize(list_cap) == hipSuccess && vals_b.resize(list_cap) == hipSuccess && temp.resize(temp_bytes ? temp_bytes : 1) == hipSuccess)
+        return true;
+      (void)hipGetLastError();
+      release();
+      return false;
+    }
   } lane_scratch[kSlots], lane_scratch_dev;  // per pipeline slot / for ngsld_run_device
-  PinBuf<double> h_xstage[2];
-  // A store that has to be BUILT is built by a thread of its own, in site order, while the run that asked for it goes on: a
-  // launch's device-side replay needs the sites up to the end of its last row's window only (exact_frontier), and the build
-  // (~0.25 us per individual and site) stays ahead of the pipeline (pair kernel + replay of the rows of those sites).  A run
-  // that started the build waits for its end before it returns: the registered source is read during runs only.
-  std::thread exact_thread;
-  std::atomic<int> exact_state{0};          // 0 no store, 1 being built, 2 complete (every site + the lane kernel's copy where it fits), -1 the build failed
-  std::atomic<uint64_t> exact_frontier{0};  // sites [0, exact_frontier) of d_xplanes / d_xmaf are on the device
-  std::atomic<bool> exact_cancel{false};
-  std::mutex exact_mu;                      // exact_cv, exact_rc, exact_msg
-  std::condition_variable exact_cv;
-  int exact_rc = 0;
-  std::string exact_msg;
-  hipStream_t exact_stream = nullptr;       // the builder's uploads
-  ReplayPool exact_pool;                    // the builder's threads (replay_pool is the run's: host-only pairs beside the build)
-  bool exact_ready = false, exact_alias = false;  // exact_ready: the run's view -- complete, errors collected
-  bool exact_failed = false;           // the device had no room for this matrix' store: host replay
-  int exact_mode = 1;                  // NGSLD_EXACT_STORE / ngsld_set_exact_store: 0 never (host replay only), 1 when it pays (default), 2 at the first flagged pair
-  double exact_build_s = 0.0;          // host seconds the store of this matrix took to build (0: an alias, or not built)
   uint64_t host_replayed_total = 0;    // pairs the host threads replayed since the matrix was set (what the decision to build looks at)
   uint64_t flagged_pairs = 0;          // pairs the kernels of the last run flagged
   bool slot_dev_applied[kSlots] = {false, false, false};  // this slot's launch had the device-side replay right behind its pair kernels
@@ -657,37 +643,34 @@ int fetch_replay_site(ngsld_ctx *c, uint64_t s, std::vector<double> &tmp, Replay
 // dev_applied: the device-side replay of likelihood matrices ran behind the launch -- what is left are its host-only pairs
 int flagged_records(ngsld_ctx *c, const uint32_t *h_head, const uint32_t *d_flags, uint32_t cap, uint64_t n,
                     std::vector<uint64_t> &recs, bool dev_applied = false);
-// likelihood matrices: can the flagged pairs of this context's runs be replayed on the device at all / right now?
 // room on the device for `need_bytes` more: hipMemGetInfo's free memory (less device_margin) and, where a cap is set
 // (ngsld_set_memory_budget), what the process has taken since against the cap (less budget_margin)
 bool room_for(uint64_t need_bytes, uint64_t device_margin, uint64_t budget_margin);
+// likelihood matrices: can the flagged pairs of this context's runs be replayed on the device at all?
 bool lkl_device_eligible(const ngsld_ctx *c);
-bool exact_store_is_free(const ngsld_ctx *c);
-// the store there or on its way (device_replay_lkl may be asked for launches whose sites it covers)
-inline bool exact_store_started(const ngsld_ctx *c) { return c->exact_state.load() >= 1; }
-// starts the build where there is something to build (idempotent); the alias forms are complete at once
-int start_exact_store(ngsld_ctx *c);
+bool lkl_device_ready(const ngsld_ctx *c);  // ... and right behind a launch: the exact store is there, on its way, or costs nothing
 int reserve_device_run(ngsld_ctx *c, uint64_t n_records);  // ngsld_run_device's own buffers for launches of up to n records, once
-// waits until sites [0, need_sites) are on the device (need_sites >= n_sites: until the store is complete); *have = false when
-// there is no store to be had (no room on the device: host replay); an error of the build comes back as the return value
-int wait_exact_store(ngsld_ctx *c, uint64_t need_sites, bool *have);
-int ensure_exact_store(ngsld_ctx *c);  // start + wait for all of it
-void stop_exact_store(ngsld_ctx *c);   // the matrix or its source changes, the context goes: the builder is cancelled and joined
 // sites a launch over rows [r0, r1) reads: up to the furthest window end among its rows (a row a filter emptied ends at itself)
 inline uint64_t exact_sites_needed(const ngsld_ctx *c, uint64_t r0, uint64_t r1) {
   uint64_t need = r1;
   for (uint64_t r = r0; r < r1 && r < c->h_row_end.size(); ++r) need = std::max<uint64_t>(need, c->h_row_end[r]);
   return std::min<uint64_t>(need, c->n_sites);
 }
-// should a run that has `pending` flagged pairs for the host build the store instead?
-bool exact_store_wanted(const ngsld_ctx *c, uint64_t pending);
-// flag_text: the launch's records become text (PairArgs::flag_text)
-// start + wait for the launch's sites + device_replay_lkl; *applied says whether the replay was launched (false: no store to be had)
-int try_device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                          ngsld_rec_ext *d_ext, hipStream_t st, bool flag_text, int slot, bool *applied, uint64_t need_sites);
-// slot: the pipeline slot whose pair list the launch uses (-1: ngsld_run_device's)
-int device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                      ngsld_rec_ext *d_ext, hipStream_t st, bool flag_text, int slot);
+// One launch as the device-side replays see it, right behind its pair kernels on their stream.
+struct ReplayLaunch {
+  uint32_t *d_flags;      // its flag buffer, with `cap` list entries
+  uint32_t cap;
+  uint64_t out_base, n;   // plan index of its record 0; its records
+  ngsld_rec_std *d_std;   // where it wrote (device, or pinned host memory)
+  ngsld_rec_ext *d_ext;
+  hipStream_t st;
+  bool flag_text;         // its records become text (PairArgs::flag_text)
+  int slot;               // the pipeline slot whose lane scratch it uses (-1: ngsld_run_device's)
+};
+// store.start + store.wait for the launch's sites + device_replay_lkl; *applied says whether the replay was launched (false: no store to be had)
+int try_device_replay_lkl(ngsld_ctx *c, const ReplayLaunch &l, bool *applied, uint64_t need_sites);
+int device_replay_lkl(ngsld_ctx *c, const ReplayLaunch &l);
+int device_replay(ngsld_ctx *c, const ReplayLaunch &l);  // called genotypes (flag_text is not looked at)
 int replay_flagged(ngsld_ctx *c, const std::vector<uint64_t> &recs, uint64_t base, ngsld_rec_std *h_std,
                    ngsld_rec_ext *h_ext, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext, hipStream_t st,
                    std::vector<uint32_t> *sites1 = nullptr, std::vector<uint32_t> *sites2 = nullptr);
@@ -695,8 +678,6 @@ int reset_flags(ngsld_ctx *c, DevBuf<uint32_t> &buf, uint64_t n, uint32_t cap, h
 // the head of a flag buffer (counters + lists) into the pinned host buffer h_head, by a small kernel on `st`
 // with_list == false: the launch had the device-side replay of likelihood matrices behind it (the listed pairs are settled)
 int send_flag_head(ngsld_ctx *c, const uint32_t *d_flags, uint32_t *h_head, uint32_t cap, hipStream_t st, bool with_list = true);
-int device_replay(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                  ngsld_rec_ext *d_ext, hipStream_t st, int slot);
 int finish_device_run(ngsld_ctx *c);  // waits for a run left on a caller's stream and replays what it flagged
 
 }  // namespace eng

@@ -29,7 +29,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
     const int rcp = finish_device_run(c);
     if (rcp != NGSLD_OK) return rcp;
   }
-  stop_exact_store(c);  // (the builder of the last matrix' exact store, if it is still at it)
+  c->store.reset();  // (the exact store of the device-side replay belongs to a matrix: its builder, if still at it, its buffers, its failure)
   c->have_geno = false;
   c->planned = false;
   c->clear_blocks();
@@ -37,17 +37,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
   c->replay_read = nullptr;  // and so does the replay source
   c->replay_user = nullptr;
   c->replay_matrix = nullptr;
-  c->exact_ready = false;    // ... and the exact store of the device-side replay
-  c->exact_alias = false;
-  c->exact_failed = false;
-  c->exact_build_s = 0.0;
   c->host_replayed_total = 0;
-  c->d_xplanes.release();
-  c->d_xmaf.release();
-  c->d_xT.release();
-  c->d_xdepth.release();
-  c->d_xperm.release();
-  c->xT_ready = false;
   // (the buffers of a grouped text run -- records, lengths, text of up to 2^25 pairs -- belong to the matrix they were sized for)
   for (int k = 0; k < 2; ++k) {
     c->d_group_std[k].release();
@@ -312,16 +302,14 @@ int ngsld_create(int device, ngsld_ctx **out) {
 void ngsld_destroy(ngsld_ctx *c) {
   if (c == nullptr) return;
   if (c->reserve_thread.joinable()) c->reserve_thread.join();
-  stop_exact_store(c);
+  c->store.destroy();
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  if (c->exact_stream) (void)hipStreamDestroy(c->exact_stream);
   c->d_planes.release(); c->d_maf.release(); c->d_mean.release(); c->d_rsx.release(); c->d_sc4.release(); c->d_dose_sum.release(); c->d_runs.release(); c->d_skip.release(); c->d_skip_count.release();
   for (auto &b : c->d_moments) b.release();
   for (auto &e : c->moments_done)
     if (e) (void)hipEventDestroy(e);
   c->d_hard_masks.release(); c->d_hard_u.release(); c->d_all_hard.release();
-  c->d_xplanes.release(); c->d_xmaf.release(); c->d_xT.release(); c->d_xdepth.release(); c->d_xperm.release(); c->h_xstage[0].release(); c->h_xstage[1].release();
   c->lane_scratch_dev.release();
   for (int k = 0; k < ngsld_ctx::kSlots; ++k) c->lane_scratch[k].release();
   c->d_labels.release(); c->d_scan_tmp.release(); c->d_scan_tmp_b.release(); c->d_label_off.release(); c->d_cum.release(); c->d_infc.release();

@@ -111,24 +111,18 @@ bool locate_record(const ngsld_ctx *c, uint64_t rec, uint32_t *s1, uint32_t *s2)
 // device's own planes (already normalised normal-space values; exact for ngsld_set_geno_lkl input).
 int fetch_replay_site(ngsld_ctx *c, uint64_t s, std::vector<double> &tmp, ReplaySite *out) {
   const uint64_t n = c->n_ind;
-  if (c->replay_matrix != nullptr) {  // the caller's own array, read in place
-    const double *v = c->replay_matrix + s * 3 * n;
+  const double *v = c->replay_matrix != nullptr ? c->replay_matrix + s * 3 * n : nullptr;  // the caller's own array, read in place
+  if (v == nullptr && c->replay_read != nullptr) {
+    tmp.resize(3 * n);
+    std::lock_guard<std::mutex> g(c->replay_mu);
+    if (c->replay_read(c->replay_user, s, 1, tmp.data()) != 0) return NGSLD_ERR_SINK;
+    v = tmp.data();
+  }
+  if (v != nullptr) {
     if (c->normalised)
       replay_site_from_lkl(v, c->h_maf[s], n, out);
     else
       replay_site_from_raw(v, n, c->gopts, out);
-    return NGSLD_OK;
-  }
-  if (c->replay_read != nullptr) {
-    tmp.resize(3 * n);
-    {
-      std::lock_guard<std::mutex> g(c->replay_mu);
-      if (c->replay_read(c->replay_user, s, 1, tmp.data()) != 0) return NGSLD_ERR_SINK;
-    }
-    if (c->normalised)
-      replay_site_from_lkl(tmp.data(), c->h_maf[s], n, out);
-    else
-      replay_site_from_raw(tmp.data(), n, c->gopts, out);
     return NGSLD_OK;
   }
   // (pinned staging: a pageable copy would be staged by the runtime; while a pair kernel of the next batch has the device
@@ -403,353 +397,34 @@ int reset_flags(ngsld_ctx *c, DevBuf<uint32_t> &buf, uint64_t n, uint32_t cap, h
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Likelihood matrices: the exact store and the device-side replay (ld_replay_lkl.hip)
+// Likelihood matrices: the device-side replay (ld_replay_lkl.hip) on the exact store (exact_store.h)
 // ---------------------------------------------------------------------------------------------------------------
 
 bool lkl_device_eligible(const ngsld_ctx *c) {
   // (beyond 4,096 individuals the wavefront-per-pair kernel has no shape: the lanes take such cohorts -- where their copy of the
-  // store cannot be had, start_exact_store gives the matrix up to the host)
+  // store cannot be had, ExactStore::start gives the matrix up to the host)
   return c->replay_on && c->replay_device && c->exact_mode != 0 && c->have_geno && c->cfg.kernel != kHard;
 }
 
-// the planes ARE the store: the caller's own normal-space values (ngsld_set_geno_lkl), or no source to build another from
-bool exact_store_is_free(const ngsld_ctx *c) {
-  return c->normalised || (c->replay_matrix == nullptr && c->replay_read == nullptr);
-}
+bool lkl_device_ready(const ngsld_ctx *c) { return lkl_device_eligible(c) && (c->store.started() || ExactStore::is_free(c)); }
 
-// Host replay costs ~0.15 us per individual and pair on one thread, the store ~0.25 us per individual and SITE (17 libm calls
-// per triple: read_geno's log + post_prob, est_maf's post_prob + exp, main's exp), once: it pays as soon as the host would
-// otherwise replay more pairs than half the matrix has sites.
-bool exact_store_wanted(const ngsld_ctx *c, uint64_t pending) {
-  if (!lkl_device_eligible(c) || c->exact_failed) return false;
-  if (exact_store_started(c) || exact_store_is_free(c)) return pending > 0;
-  if (c->exact_mode >= 2) return pending > 0;
-  return c->host_replayed_total + pending > std::max<uint64_t>(4096, c->n_sites / 2);
-}
-
-// The individual-major copy for the lane-per-pair kernel, where the device has room for the matrix once more: its memory
-static bool alloc_lane_store(ngsld_ctx *c) {
-  c->xT_ready = false;
-  const size_t elems = (size_t)c->n_sites * c->n_ind * 3;
-  // (4 GB of the device left for what comes later -- text buffers, the lanes' list and sort scratch; under a cap: half a GB of it)
-  if (!room_for(elems * sizeof(double), 4ull << 30, 512ull << 20)) return false;
-  // The order of the sites in the copy: the RARE ones first (folded frequency below 1/32, or no frequency), the others behind,
-  // each class in site order.  The pairs the lanes replay are pairs with a (nearly) monomorphic site, a wavefront's 64 lanes hold
-  // a few neighbouring rare sites x 8 partners they share (replay_keys_kernel), and per individual the rare sites' triples are
-  // 24 bytes each out of a cache line of their own while they stand among 32 consecutive sites: the launch fetched 1.3 TB
-  // through an L2 that hit 18 % of the time (profiles/r06/replay_lane).  Standing together they share their lines: same-box
-  // 612.5 / 613.3 -> 601.2 / 602.5 ms a pass at 20 % monomorphic sites (profiles/r06/lane/perm_ab.txt).
-  std::vector<uint32_t> perm(c->n_sites);
-  {
-    uint32_t n_rare = 0;
-    auto rare = [&](uint64_t s) {
-      const double m = c->h_maf[s], r = m <= 0.5 ? m : 1 - m;
-      return !(r >= 0.03125);
-    };
-    for (uint64_t s = 0; s < c->n_sites; ++s) n_rare += rare(s) ? 1u : 0u;
-    uint32_t at_rare = 0, at_rest = n_rare;
-    for (uint64_t s = 0; s < c->n_sites; ++s) perm[s] = rare(s) ? at_rare++ : at_rest++;
-  }
-  if (c->d_xT.resize(elems) != hipSuccess || c->d_xdepth.resize(c->n_sites) != hipSuccess ||
-      hipMemset(c->d_xdepth.p, 0, c->n_sites * sizeof(uint32_t)) != hipSuccess ||
-      c->d_xperm.resize(c->n_sites) != hipSuccess ||
-      hipMemcpy(c->d_xperm.p, perm.data(), c->n_sites * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    c->d_xT.release();
-    c->d_xperm.release();
-    return false;
-  }
-  return true;
-}
-
-// ... and all of it at once from planes that are a store already (the alias forms), on stream st, synchronised
-static hipError_t build_lane_store(ngsld_ctx *c, hipStream_t st) {
-  if (!alloc_lane_store(c)) return hipSuccess;
-  hipError_t e = launch_transpose_store(c->exact_alias ? c->d_planes.p : c->d_xplanes.p, 3ull * c->np, c->np, (uint32_t)c->n_ind, c->n_sites,
-                                        c->d_xT.p, c->d_xdepth.p, c->d_xperm.p, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return e;
-  c->xT_ready = true;
-  return hipSuccess;
-}
-
-// a chunk of the store from pinned host memory into place (site_elems is even: np is a multiple of 8)
-__global__ __launch_bounds__(256) void store_chunk_kernel(const double *__restrict__ src, double *__restrict__ dst, uint64_t n,
-                                                          const double *__restrict__ src_maf, double *__restrict__ dst_maf, uint64_t n_maf) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, T = (uint64_t)gridDim.x * blockDim.x;
-  const double2 *s2 = reinterpret_cast<const double2 *>(src);
-  double2 *d2 = reinterpret_cast<double2 *>(dst);
-  for (uint64_t i = t; i < n / 2; i += T) d2[i] = s2[i];
-  if (t == 0 && (n & 1)) dst[n - 1] = src[n - 1];
-  for (uint64_t i = t; i < n_maf; i += T) dst_maf[i] = src_maf[i];
-}
-
-// The builder (ngsld_ctx::exact_thread): the registered source through the host's libm, chunk by chunk in site order -- two
-// pinned staging buffers, a chunk's upload (and its transposition into the lane kernel's copy) beside the next chunk's
-// arithmetic --, the frontier published as the uploads land.  Touches nothing of the context a run touches but the store's own buffers and atomics.
-static void exact_builder(ngsld_ctx *c) {
-  Range range_("ngsld:exact store (host libm -> device)");
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = NGSLD_OK;
-  std::string msg;
-  auto hip_bad = [&](hipError_t e, const char *what) {
-    if (e == hipSuccess) return false;
-    (void)hipGetLastError();
-    rc = NGSLD_ERR_DEVICE;
-    msg = std::string(what) + ": " + hipGetErrorString(e);
-    return true;
-  };
-  try {
-    const uint64_t n = c->n_sites, ni = c->n_ind, np = c->np, site_elems = 3 * np;
-    uint64_t chunk = std::max<uint64_t>(1, (32ull << 20) / (site_elems * sizeof(double)));
-    uint64_t slow_us = 0;  // tests: small chunks, a builder the run has to wait for
-    if (const char *e = test_knob("EXACT_CHUNK_SITES")) chunk = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
-    if (const char *e = test_knob("EXACT_SLOW_US")) slow_us = std::strtoull(e, nullptr, 10);
-    if (chunk > n) chunk = n;
-    struct Events {  // (destroyed on every way out)
-      hipEvent_t e[2] = {nullptr, nullptr};
-      ~Events() {
-        for (hipEvent_t x : e)
-          if (x) (void)hipEventDestroy(x);
-      }
-    } up;
-    bool ok = !hip_bad(hipSetDevice(c->device), "exact store");
-    if (ok && c->exact_stream == nullptr) {
-      // a HIGH-PRIORITY stream: the runtime gives it a hardware queue of that priority instead of a share in one of the run's
-      // four -- where a chunk's upload stood behind an 80 ms replay kernel of the run, which itself waited for the builder's
-      // frontier: one chunk per batch, 120,000 x 2,000 built in 5.1 s instead of 0.4
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
-        (void)hipGetLastError();
-        least = greatest = 0;
-      }
-      ok = !hip_bad(hipStreamCreateWithPriority(&c->exact_stream, hipStreamNonBlocking, greatest), "exact store stream");
-    }
-    for (int k = 0; k < 2 && ok; ++k) {
-      ok = !hip_bad(c->h_xstage[k].resize((size_t)chunk * (site_elems + 1)), "exact store staging") &&  // (+ 1: the site's est_maf behind the planes)
-           !hip_bad(hipEventCreateWithFlags(&up.e[k], hipEventDisableTiming), "exact store event");
-    }
-    hipStream_t st = c->exact_stream;
-    const int T = c->replay_threads > 0 ? c->replay_threads : (int)std::min<unsigned>(32u, usable_threads());
-    std::vector<double> raw_chunk;  // (callback source: the chunk's raw values, fetched with one call)
-    uint64_t k = 0, prev_end = 0;
-    for (uint64_t s0 = 0; s0 < n && ok && !c->exact_cancel.load(); s0 += chunk, ++k) {
-      const int b = (int)(k & 1);
-      const uint64_t m = std::min(chunk, n - s0);
-      // (buffer b was last read by the upload of chunk k - 2, whose event was waited for when chunk k - 1 was issued)
-      const double *raw = nullptr;
-      if (c->replay_matrix != nullptr) {
-        raw = c->replay_matrix + s0 * 3 * ni;
-      } else {
-        raw_chunk.resize((size_t)m * 3 * ni);
-        std::lock_guard<std::mutex> g(c->replay_mu);
-        if (c->replay_read(c->replay_user, s0, m, raw_chunk.data()) != 0) {
-          rc = NGSLD_ERR_SINK;
-          msg = "the replay source callback failed";
-          ok = false;
-          break;
-        }
-        raw = raw_chunk.data();
-      }
-      if (slow_us) std::this_thread::sleep_for(std::chrono::microseconds(slow_us));
-      double *stage = c->h_xstage[b].p, *stage_maf = stage + (size_t)chunk * site_elems;
-      const int Tm = (int)std::min<uint64_t>((uint64_t)T, m);
-      std::vector<int> good((size_t)Tm, 1);
-      c->exact_pool.run(Tm, [&](int t) {
-        try {
-          for (uint64_t s = m * (uint64_t)t / (uint64_t)Tm; s < m * (uint64_t)(t + 1) / (uint64_t)Tm; ++s)
-            replay_site_planes(raw + s * 3 * ni, ni, c->gopts, np, stage + s * site_elems, &stage_maf[s]);
-        } catch (...) {
-          good[(size_t)t] = 0;
-        }
-      });
-      for (int t = 0; t < Tm; ++t)
-        if (!good[(size_t)t]) {
-          rc = NGSLD_ERR_NOMEM;
-          msg = "out of host memory";
-          ok = false;
-        }
-      if (!ok) break;
-      // (a KERNEL reads the pinned chunk over the host link, not hipMemcpyAsync: an SDMA copy can queue behind the run's text
-      // copies on that engine, each of which waits for its batch's kernels -- send_flag_head)
-      double *stage_dev = nullptr;
-      if (hip_bad(hipHostGetDevicePointer((void **)&stage_dev, stage, 0), "exact store upload")) {
-        ok = false;
-        break;
-      }
-      hipLaunchKernelGGL(store_chunk_kernel, dim3(512), dim3(256), 0, st, stage_dev, c->d_xplanes.p + s0 * site_elems, (uint64_t)m * site_elems,
-                         stage_dev + (size_t)chunk * site_elems, c->d_xmaf.p + s0, (uint64_t)m);
-      bool sent = !hip_bad(hipGetLastError(), "exact store upload");
-      if (sent && c->xT_ready.load())  // (the lane kernel's copy of these sites, behind their planes on the same stream)
-        sent = !hip_bad(launch_transpose_store(c->d_xplanes.p, site_elems, (uint32_t)np, (uint32_t)ni, n, c->d_xT.p, c->d_xdepth.p, c->d_xperm.p, st, s0, s0 + m),
-                        "exact store, individual-major copy");
-      if (!sent || hip_bad(hipEventRecord(up.e[b], st), "exact store upload")) {
-        ok = false;
-        break;
-      }
-      if (k >= 1) {  // the chunk before this one has landed (its upload ran beside this chunk's arithmetic): publish it
-        if (hip_bad(hipEventSynchronize(up.e[b ^ 1]), "exact store upload")) {
-          ok = false;
-          break;
-        }
-        c->exact_frontier.store(prev_end);
-        c->exact_cv.notify_all();
-      }
-      prev_end = s0 + m;
-    }
-    if (c->exact_stream != nullptr) {
-      const hipError_t e = hipStreamSynchronize(c->exact_stream);
-      if (ok) ok = !hip_bad(e, "exact store upload");
-    }
-    if (ok && !c->exact_cancel.load()) {
-      c->exact_frontier.store(n);
-      c->exact_cv.notify_all();
-    }
-    c->h_xstage[0].release();  // (64 MB of pinned host memory, used once per matrix)
-    c->h_xstage[1].release();
-  } catch (...) {
-    rc = NGSLD_ERR_NOMEM;
-    msg = "out of host memory";
-  }
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  {
-    std::lock_guard<std::mutex> g(c->exact_mu);
-    c->exact_rc = rc;
-    c->exact_msg = msg;
-    c->exact_build_s = secs;
-    c->exact_state.store(rc == NGSLD_OK && !c->exact_cancel.load() ? 2 : -1);
-  }
-  c->exact_cv.notify_all();
-  if (std::getenv("NGSLD_TRACE") != nullptr)
-    std::fprintf(stderr, "[trace] exact store: %llu sites x %llu individuals through the host's libm in %.3f s (a thread of its own beside the run)\n",
-                 (unsigned long long)c->n_sites, (unsigned long long)c->n_ind, secs);
-}
-
-void stop_exact_store(ngsld_ctx *c) {
-  if (c->exact_thread.joinable()) {
-    c->exact_cancel.store(true);
-    c->exact_thread.join();
-  }
-  c->exact_cancel.store(false);
-  c->exact_state.store(0);
-  c->exact_frontier.store(0);
-  c->exact_rc = NGSLD_OK;
-  c->exact_msg.clear();
-  c->exact_ready = false;
-  c->xT_ready = false;
-  // (a new source or matrix: nothing of the old store is of use, start_exact_store allocates what it needs)
-  c->d_xplanes.release();
-  c->d_xmaf.release();
-  c->d_xT.release();
-  c->d_xperm.release();
-  c->d_xdepth.release();
-}
-
-int start_exact_store(ngsld_ctx *c) {
-  if (c->exact_state.load() != 0 || c->exact_failed) return NGSLD_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (exact_store_is_free(c)) {  // the planes ARE the store
-    c->exact_alias = true;
-    c->exact_frontier.store(c->n_sites);
-    const hipError_t e = build_lane_store(c, replay_stream_of(c));
-    if (e != hipSuccess) return hip_fail(c, e, "exact store, individual-major copy");
-    if (!c->xT_ready.load() && replay_lkl_waves((uint32_t)c->n_ind) == 0) {  // (no room for the copy the lanes read, and no other kernel for this cohort)
-      c->exact_failed = true;
-      return NGSLD_OK;
-    }
-    c->exact_state.store(2);
-    c->exact_ready = true;
-    return NGSLD_OK;
-  }
-  // (a device without room for the matrix once more: no store for this matrix -- its flagged pairs stay with the host's threads)
-  const bool pretend = test_knob("EXACT_STORE_NO_ROOM") != nullptr;
-  const bool no_room = !room_for((uint64_t)c->n_sites * (3ull * c->np + 1) * sizeof(double), 0, 256ull << 20);  // (ngsld_set_memory_budget)
-  if (pretend || no_room || c->d_xplanes.resize((size_t)c->n_sites * 3 * c->np) != hipSuccess || c->d_xmaf.resize(c->n_sites) != hipSuccess) {
-    (void)hipGetLastError();
-    c->d_xplanes.release();
-    c->d_xmaf.release();
-    c->exact_failed = true;
-    return NGSLD_OK;
-  }
-  if (c->exact_thread.joinable()) c->exact_thread.join();  // (a builder that ended by itself)
-  c->exact_alias = false;
-  c->xT_ready = alloc_lane_store(c);  // (filled chunk by chunk behind the planes: usable as far as the frontier, like them)
-  if (!c->xT_ready.load() && replay_lkl_waves((uint32_t)c->n_ind) == 0) {  // (see the alias form above)
-    c->d_xplanes.release();
-    c->d_xmaf.release();
-    c->exact_failed = true;
-    return NGSLD_OK;
-  }
-  c->exact_cancel.store(false);
-  c->exact_frontier.store(0);
-  c->exact_state.store(1);
-  try {
-    c->exact_thread = std::thread(exact_builder, c);
-  } catch (...) {
-    c->exact_state.store(0);
-    c->exact_failed = true;  // (no thread to be had: host replay)
-  }
-  return NGSLD_OK;
-}
-
-int wait_exact_store(ngsld_ctx *c, uint64_t need_sites, bool *have) {
-  *have = false;
-  if (c->exact_failed || c->exact_state.load() == 0) return NGSLD_OK;
-  const bool all = need_sites >= c->n_sites;
-  {
-    std::unique_lock<std::mutex> lk(c->exact_mu);
-    // (the builder publishes the frontier without the lock: a short timed wait instead of a missed wake-up)
-    while (c->exact_state.load() == 1 && (all || c->exact_frontier.load() < need_sites)) c->exact_cv.wait_for(lk, std::chrono::milliseconds(1));
-    if (c->exact_state.load() == -1) {
-      const int rc = c->exact_rc;
-      const std::string msg = c->exact_msg;
-      lk.unlock();
-      if (c->exact_thread.joinable()) c->exact_thread.join();
-      c->exact_state.store(0);
-      c->exact_failed = true;  // (not again for this matrix)
-      c->d_xplanes.release();
-      c->d_xmaf.release();
-      c->d_xT.release();
-      c->d_xperm.release();
-      c->d_xdepth.release();
-      c->xT_ready = false;
-      return rc != NGSLD_OK ? fail(c, rc, msg.c_str()) : NGSLD_OK;
-    }
-  }
-  if (c->exact_state.load() == 2) {
-    if (c->exact_thread.joinable()) c->exact_thread.join();
-    c->exact_ready = true;
-  }
-  *have = true;
-  return NGSLD_OK;
-}
-
-int ensure_exact_store(ngsld_ctx *c) {
-  if (c->exact_ready) return NGSLD_OK;
-  const int rc = start_exact_store(c);
-  if (rc != NGSLD_OK) return rc;
-  bool have = false;
-  return wait_exact_store(c, c->n_sites, &have);
-}
-
-int try_device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                          ngsld_rec_ext *d_ext, hipStream_t st, bool flag_text, int slot, bool *applied, uint64_t need_sites) {
+int try_device_replay_lkl(ngsld_ctx *c, const ReplayLaunch &l, bool *applied, uint64_t need_sites) {
   *applied = false;
-  int rc = start_exact_store(c);
-  if (rc != NGSLD_OK) return rc;
+  RC_TRY(c->store.start(c));
   bool have = false;
-  rc = wait_exact_store(c, need_sites, &have);
-  if (rc != NGSLD_OK || !have) return rc;
-  rc = device_replay_lkl(c, d_flags, cap, out_base, n, d_std, d_ext, st, flag_text, slot);
-  if (rc == NGSLD_OK) *applied = true;
-  return rc;
+  RC_TRY(c->store.wait(c, need_sites, &have));
+  if (!have) return NGSLD_OK;
+  RC_TRY(device_replay_lkl(c, l));
+  *applied = true;
+  return NGSLD_OK;
 }
 
 // The flagged pairs of a launch replayed on the device (likelihood matrices), on `st` behind the pair kernels that flagged
 // them -- before the head of the flag buffer travels to the host, before text rows are formatted.  The store must be ready.
-int device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                      ngsld_rec_ext *d_ext, hipStream_t st, bool flag_text, int slot) {
-  if (!exact_store_started(c) || d_flags == nullptr || n == 0) return NGSLD_OK;
+int device_replay_lkl(ngsld_ctx *c, const ReplayLaunch &l) {
+  const auto [d_flags, cap, out_base, n, d_std, d_ext, st, flag_text, slot] = l;
+  const ExactStore &store = c->store;
+  if (!store.started() || d_flags == nullptr || n == 0) return NGSLD_OK;
   ReplayLklArgs a{};
   const size_t head = flag_head_words(cap), words = flag_bitmap_words(n);
   a.bits = d_flags + head;
@@ -768,18 +443,18 @@ int device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t ou
   a.n_items = c->n_items;
   a.n_sites = (uint32_t)c->n_sites;
   a.rec_base = out_base;
-  a.xplanes = c->exact_alias ? c->d_planes.p : c->d_xplanes.p;
+  a.xplanes = store.planes(c);
   a.site_stride = 3ull * c->np;
   a.np = c->np;
-  a.xmaf = c->exact_alias ? c->d_maf.p : c->d_xmaf.p;
+  a.xmaf = store.maf(c);
   a.n_ind = (uint32_t)c->n_ind;
   a.ignore_miss = c->params.ignore_miss_data;
   a.out_std = d_std;
   a.out_ext = d_ext;
   a.status = c->d_status.p;
   a.xt_sites = c->n_sites;
-  a.xdepth = c->d_xdepth.p;
-  a.xperm = c->d_xperm.p;
+  a.xdepth = store.lane_depth();
+  a.xperm = store.lane_perm();
   // (a launch of a few hundred thousand records -- a text batch -- stays with the wavefront-per-pair kernel: a lane takes
   // milliseconds over ONE pair, four wavefronts to a SIMD, and such a launch has no second pair for most lanes: 6 ms a batch
   // against 4, profiles/r05/e2e_uncalled_lanes_on_text_batches.json)
@@ -790,52 +465,35 @@ int device_replay_lkl(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t ou
   const uint32_t team_waves = replay_lkl_waves((uint32_t)c->n_ind);  // (0: beyond 4,096 individuals -- the lanes or nothing)
   const bool big_cohort = team_waves >= 2 || team_waves == 0;
   if (big_cohort) lanes_from = 0;
-  if (team_waves == 0 && !c->xT_ready.load()) return fail(c, NGSLD_ERR_INVALID, "device-side replay without a kernel for this cohort");
-  if (c->xT_ready && (n >= lanes_from || team_waves == 0)) {
-    a.after_lanes = 1;
+  if (team_waves == 0 && !store.has_lane_copy()) return fail(c, NGSLD_ERR_INVALID, "device-side replay without a kernel for this cohort");
+  if (store.has_lane_copy() && (n >= lanes_from || team_waves == 0)) {
     // one lane per pair wherever the individual-major copy is there: the launch's bitmap becomes a list of located pairs (the
     // bits listed are cleared), the lanes work through it; what stays in the bitmap -- ill-conditioned Pearson moments, pairs
     // beyond the list -- is the wavefront-per-pair kernel's, as everything is without the copy
     ngsld_ctx::LaneScratch &ls = slot < 0 ? c->lane_scratch_dev : c->lane_scratch[slot];
     const uint64_t list_cap = std::min<uint64_t>(n, 1ull << 26);
-    const size_t temp_bytes = replay_sort_temp_bytes(list_cap, (uint32_t)c->n_sites);
     // (the lanes' scratch -- 40 bytes per record of the launch + the sort's own -- is something the run can do without: where the
     // device has no room for it the launch stays with the wavefront-per-pair kernel, or the host where that has no shape)
-    const bool have_scratch = ls.list.resize(list_cap) == hipSuccess && ls.keys_a.resize(list_cap) == hipSuccess &&
-                              ls.keys_b.resize(list_cap) == hipSuccess && ls.vals_a.resize(list_cap) == hipSuccess &&
-                              ls.vals_b.resize(list_cap) == hipSuccess && ls.temp.resize(temp_bytes ? temp_bytes : 1) == hipSuccess;
-    if (!have_scratch) {
-      (void)hipGetLastError();
-      ls.list.release(); ls.keys_a.release(); ls.keys_b.release(); ls.vals_a.release(); ls.vals_b.release(); ls.temp.release();
-      a.after_lanes = 0;
-      if (team_waves == 0) {
-        HIP_TRY(c, launch_replay_leftover(a, st));
-        return NGSLD_OK;
+    if (ls.reserve(list_cap, c->n_sites)) {
+      a.after_lanes = 1;
+      HIP_TRY(c, launch_replay_expand(a, ls.list.p, list_cap, st));
+      HIP_TRY(c, launch_replay_sort(a, ls.list.p, list_cap, ls.keys_a.p, ls.keys_b.p, ls.vals_a.p, ls.vals_b.p, ls.temp.p, ls.temp_bytes, st));
+      int lane_waves = n >= (1ull << 22) ? 4 : 1;
+      if (n < (1ull << 22) && team_waves != 0) {  // (no wavefront kernel to hand a long pair back to: no cap)
+        a.lane_iter_cap = 12;
+        if (const char *v = test_knob("LANE_ITER_CAP")) a.lane_iter_cap = (uint32_t)std::strtoul(v, nullptr, 10);  // (tests: hand-backs on every pair)
       }
-      HIP_TRY(c, launch_replay_lkl(a, c->n_cus, st));
-      return NGSLD_OK;
+      HIP_TRY(c, launch_replay_lanes(a, ls.list.p, ls.vals_b.p, store.lane_copy(), c->n_cus, lane_waves, st));
     }
-    HIP_TRY(c, launch_replay_expand(a, ls.list.p, list_cap, st));
-    HIP_TRY(c, launch_replay_sort(a, ls.list.p, list_cap, ls.keys_a.p, ls.keys_b.p, ls.vals_a.p, ls.vals_b.p, ls.temp.p, temp_bytes, st));
-    int lane_waves = n >= (1ull << 22) ? 4 : 1;
-    if (n < (1ull << 22) && team_waves != 0) {  // (no wavefront kernel to hand a long pair back to: no cap)
-      a.lane_iter_cap = 12;
-      if (const char *v = test_knob("LANE_ITER_CAP")) a.lane_iter_cap = (uint32_t)std::strtoul(v, nullptr, 10);  // (tests: hand-backs on every pair)
-    }
-    HIP_TRY(c, launch_replay_lanes(a, ls.list.p, ls.vals_b.p, c->d_xT.p, c->n_cus, lane_waves, st));
   }
-  if (team_waves == 0)
-    HIP_TRY(c, launch_replay_leftover(a, st));
-  else
-    HIP_TRY(c, launch_replay_lkl(a, c->n_cus, st));
+  HIP_TRY(c, team_waves == 0 ? launch_replay_leftover(a, st) : launch_replay_lkl(a, c->n_cus, st));
   return NGSLD_OK;
 }
 
 // Called-genotype matrices: the flagged pairs of a launch replayed on the device (ld_replay.hip), right behind the pair
 // kernels on their stream -- before the head of the flag buffer travels to the host, before text rows are formatted.
-// out_base: plan index of the launch's record 0; d_std / d_ext: where the launch wrote (device, or pinned host memory).
-int device_replay(ngsld_ctx *c, uint32_t *d_flags, uint32_t cap, uint64_t out_base, uint64_t n, ngsld_rec_std *d_std,
-                  ngsld_rec_ext *d_ext, hipStream_t st, int slot) {
+int device_replay(ngsld_ctx *c, const ReplayLaunch &l) {
+  const auto [d_flags, cap, out_base, n, d_std, d_ext, st, flag_text, slot] = l;
   if (!c->replay_on || !c->replay_device || c->cfg.kernel != kHard || d_flags == nullptr || n == 0) return NGSLD_OK;
   // A launch that flags more pairs than its list holds (every pair of a monomorphic called site): the bitmap is turned into a
   // list of located pairs and a second kernel works through that -- both leave at once unless the list did overflow
@@ -905,16 +563,8 @@ int reserve_device_run(ngsld_ctx *c, uint64_t n) {
   const uint32_t cap = flag_cap_for(n);
   HIP_TRY(c, c->d_flags_dev.resize(flag_words(n, cap)));
   HIP_TRY(c, c->h_flags_dev.resize(flag_head_words(cap)));
-  if (lkl_device_eligible(c)) {
-    ngsld_ctx::LaneScratch &ls = c->lane_scratch_dev;
-    const uint64_t list_cap = std::min<uint64_t>(n, 1ull << 26);
-    const size_t temp_bytes = replay_sort_temp_bytes(list_cap, (uint32_t)c->n_sites);
-    if (ls.list.resize(list_cap) != hipSuccess || ls.keys_a.resize(list_cap) != hipSuccess || ls.keys_b.resize(list_cap) != hipSuccess ||
-        ls.vals_a.resize(list_cap) != hipSuccess || ls.vals_b.resize(list_cap) != hipSuccess || ls.temp.resize(temp_bytes ? temp_bytes : 1) != hipSuccess) {
-      (void)hipGetLastError();  // (the launches will find out themselves, and do without the lanes)
-      ls.release();
-    }
-  }
+  // (no room: the launches will find out themselves, and do without the lanes)
+  if (lkl_device_eligible(c)) (void)c->lane_scratch_dev.reserve(std::min<uint64_t>(n, 1ull << 26), c->n_sites);
   return NGSLD_OK;
 }
 
@@ -931,22 +581,19 @@ int finish_device_run(ngsld_ctx *c) {
   if (c->h_flags_dev.p[0] == 0) return NGSLD_OK;
   const uint64_t base = c->h_row_off[c->dev_run.s1_begin], n = c->h_row_off[c->dev_run.s1_end] - base;
   bool applied = c->dev_run.dev_applied;
-  if (!applied && exact_store_wanted(c, c->h_flags_dev.p[0] - c->h_flags_dev.p[1])) {
+  if (!applied && c->store.wanted(c, c->h_flags_dev.p[0] - c->h_flags_dev.p[1])) {
     // a likelihood matrix that flags more pairs than the host should replay: the exact store is built (once per matrix) and
     // the pairs are replayed on the device, behind the kernels on their stream
-    int rcx = try_device_replay_lkl(c, c->d_flags_dev.p, c->flag_cap_dev, base, n, c->dev_run.d_std, c->dev_run.d_ext, c->dev_run.st,
-                                    c->dev_run_flag_text, -1, &applied, c->n_sites);
-    if (rcx != NGSLD_OK) return rcx;
+    const ReplayLaunch l{c->d_flags_dev.p, c->flag_cap_dev, base, n, c->dev_run.d_std, c->dev_run.d_ext, c->dev_run.st, c->dev_run_flag_text, -1};
+    RC_TRY(try_device_replay_lkl(c, l, &applied, c->n_sites));
     if (applied) {
-      rcx = send_flag_head(c, c->d_flags_dev.p, c->h_flags_dev.p, c->flag_cap_dev, c->dev_run.st, false);
-      if (rcx != NGSLD_OK) return rcx;
+      RC_TRY(send_flag_head(c, c->d_flags_dev.p, c->h_flags_dev.p, c->flag_cap_dev, c->dev_run.st, false));
       HIP_TRY(c, hipStreamSynchronize(c->dev_run.st));
     }
   }
   const double t_dev = ms();
   std::vector<uint64_t> recs;
-  const int rcf = flagged_records(c, c->h_flags_dev.p, c->d_flags_dev.p, c->flag_cap_dev, n, recs, applied);
-  if (rcf != NGSLD_OK) return rcf;
+  RC_TRY(flagged_records(c, c->h_flags_dev.p, c->d_flags_dev.p, c->flag_cap_dev, n, recs, applied));
   const double t_list = ms();
   const int rcr = replay_flagged(c, recs, base, nullptr, nullptr, c->dev_run.d_std, c->dev_run.d_ext, c->dev_run.st);
   if (trace)
@@ -960,29 +607,19 @@ int finish_device_run(ngsld_ctx *c) {
 
 extern "C" {
 
-int ngsld_set_replay_source(ngsld_ctx *c, ngsld_read_sites_fn read, void *user) {
+static int set_replay_source(ngsld_ctx *c, const double *matrix, ngsld_read_sites_fn read, void *user) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   if (!c->have_geno) return fail(c, NGSLD_ERR_INVALID, "set the genotype data before its replay source");
-  stop_exact_store(c);  // (the exact store is built from the source)
-  c->replay_matrix = nullptr;
+  c->store.stop();  // (the exact store is built from the source)
+  c->replay_matrix = matrix;
   c->replay_read = read;
   c->replay_user = user;
   c->planned = false;  // a --min_maf tie is settled at plan time
   c->clear_blocks();
   return NGSLD_OK;
 }
-
-int ngsld_set_replay_matrix(ngsld_ctx *c, const double *values) {
-  if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (!c->have_geno) return fail(c, NGSLD_ERR_INVALID, "set the genotype data before its replay source");
-  stop_exact_store(c);  // (the exact store is built from the source)
-  c->replay_matrix = values;
-  c->replay_read = nullptr;
-  c->replay_user = nullptr;
-  c->clear_blocks();
-  c->planned = false;  // a --min_maf tie is settled at plan time
-  return NGSLD_OK;
-}
+int ngsld_set_replay_source(ngsld_ctx *c, ngsld_read_sites_fn read, void *user) { return set_replay_source(c, nullptr, read, user); }
+int ngsld_set_replay_matrix(ngsld_ctx *c, const double *values) { return set_replay_source(c, values, nullptr, nullptr); }
 
 int ngsld_set_replay(ngsld_ctx *c, int enable) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
@@ -1006,9 +643,9 @@ int ngsld_replay_info(ngsld_ctx *c, ngsld_replay_stats_t *out) {
   out->pairs_on_device = c->replayed_on_device;
   out->pairs_on_host = c->replayed_pairs - c->replayed_on_device;
   out->sites_reevaluated = c->replayed_sites;
-  out->exact_store = c->exact_state.load() == 2 ? (c->exact_alias ? 1 : 2) : 0;
+  out->exact_store = c->store.kind();
   out->text_rows_patched = (int32_t)std::min<uint64_t>(c->text_rows_patched, 0x7fffffffull);
-  out->exact_store_build_s = c->exact_build_s;
+  out->exact_store_build_s = c->store.build_seconds();
   out->sites_degenerate = c->h_skip_count;
   return NGSLD_OK;
 }
@@ -1024,8 +661,7 @@ int ngsld_finish_device(ngsld_ctx *c) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // (a failure some earlier call already reported must not surface as a launch's "last error")
-  const int rc = finish_device_run(c);
-  if (rc != NGSLD_OK) return rc;
+  RC_TRY(finish_device_run(c));
   return check_status(c);
 } NGSLD_CATCH(c)
 

@@ -123,7 +123,7 @@ PairArgs make_args(ngsld_ctx *c, uint64_t r0, uint64_t r1, ngsld_rec_std *d_std,
   a.pearson_on_device = lkl_device_eligible(c) ? 1 : 0;
   // the pairs of degenerate sites (sc4[.][3]) skip their EM: every one of them is flagged and the exact-order replay is their
   // only evaluation -- on while the device-side replay of likelihood matrices can take them
-  a.skip_degenerate = (d_flags != nullptr && c->h_skip_count > 0 && c->skip_on && lkl_device_eligible(c) && !c->exact_failed) ? 1 : 0;
+  a.skip_degenerate = (d_flags != nullptr && c->h_skip_count > 0 && c->skip_on && lkl_device_eligible(c) && !c->store.failed()) ? 1 : 0;
   a.planes = c->d_planes.p;
   a.site_stride = 3ull * c->np;
   a.np = c->np;
@@ -227,8 +227,7 @@ int ngsld_run_device(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, void *d_s
   c->text_rows_patched = 0;
   if (c->replay_on) {
     c->flag_cap_dev = flag_cap_for(c->timed_pairs);
-    const int rcf = reset_flags(c, c->d_flags_dev, c->timed_pairs, c->flag_cap_dev, st);
-    if (rcf != NGSLD_OK) return rcf;
+    RC_TRY(reset_flags(c, c->d_flags_dev, c->timed_pairs, c->flag_cap_dev, st));
     HIP_TRY(c, c->h_flags_dev.resize(flag_head_words(c->flag_cap_dev)));
   }
   // one launch per <= 2^31-1 workgroups; rows are cut so that each launch's grid fits
@@ -238,10 +237,8 @@ int ngsld_run_device(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, void *d_s
     r0 = rows_within(c->h_item_off, r0, s1_end, max_items);
     cuts.push_back(r0);
   }
-  if (uses_runs(c->cfg.kernel)) {  // (big launches: whole-row runs, whatever an earlier ngsld_run cut them to, short ones at each launch's end)
-    const int rcr = build_runs(c, kRunItems, cuts);
-    if (rcr != NGSLD_OK) return rcr;
-  }
+  // (big launches: whole-row runs, whatever an earlier ngsld_run cut them to, short ones at each launch's end)
+  if (uses_runs(c->cfg.kernel)) RC_TRY(build_runs(c, kRunItems, cuts));
   uint64_t r0 = s1_begin;
   for (const uint64_t r1 : cuts) {
     PairArgs a = make_args(c, r0, r1, (ngsld_rec_std *)d_std, (ngsld_rec_ext *)d_ext, c->replay_on ? c->d_flags_dev.p : nullptr,
@@ -255,21 +252,16 @@ int ngsld_run_device(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, void *d_s
   }
   c->dev_run.dev_applied = false;
   if (c->replay_on) {
-    int rcd = device_replay(c, c->d_flags_dev.p, c->flag_cap_dev, c->h_row_off[s1_begin], c->timed_pairs,
-                            (ngsld_rec_std *)d_std, (ngsld_rec_ext *)d_ext, st, -1);
-    if (rcd != NGSLD_OK) return rcd;
+    const ReplayLaunch l{c->d_flags_dev.p, c->flag_cap_dev, c->h_row_off[s1_begin], c->timed_pairs, (ngsld_rec_std *)d_std, (ngsld_rec_ext *)d_ext,
+                         st, c->dev_run_flag_text, -1};
+    RC_TRY(device_replay(c, l));
     // likelihood matrices: right behind the kernels when the exact store is there (or costs nothing); a run that turns out to
     // flag many pairs without one has it built in ngsld_finish_device
-    if (lkl_device_eligible(c) && (exact_store_started(c) || exact_store_is_free(c))) {
-      rcd = try_device_replay_lkl(c, c->d_flags_dev.p, c->flag_cap_dev, c->h_row_off[s1_begin], c->timed_pairs,
-                                  (ngsld_rec_std *)d_std, (ngsld_rec_ext *)d_ext, st, c->dev_run_flag_text, -1, &c->dev_run.dev_applied,
-                                  c->dev_run_flag_text ? exact_sites_needed(c, s1_begin, s1_end) : c->n_sites);
-      if (rcd != NGSLD_OK) return rcd;
-    }
+    if (lkl_device_ready(c))
+      RC_TRY(try_device_replay_lkl(c, l, &c->dev_run.dev_applied, c->dev_run_flag_text ? exact_sites_needed(c, s1_begin, s1_end) : c->n_sites));
     // which pairs the kernels flagged (and the device has not settled itself): the counter and the list come over behind
     // them, on their stream
-    rcd = send_flag_head(c, c->d_flags_dev.p, c->h_flags_dev.p, c->flag_cap_dev, st, !c->dev_run.dev_applied);
-    if (rcd != NGSLD_OK) return rcd;
+    RC_TRY(send_flag_head(c, c->d_flags_dev.p, c->h_flags_dev.p, c->flag_cap_dev, st, !c->dev_run.dev_applied));
   }
   c->dev_run.pending = true;
   c->dev_run.s1_begin = s1_begin;
@@ -278,8 +270,7 @@ int ngsld_run_device(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, void *d_s
   c->dev_run.d_ext = (ngsld_rec_ext *)d_ext;
   c->dev_run.st = st;
   if (hip_stream == nullptr) {
-    const int rcd = finish_device_run(c);  // waits for the kernels, replays what they flagged
-    if (rcd != NGSLD_OK) return rcd;
+    RC_TRY(finish_device_run(c));  // waits for the kernels, replays what they flagged
     return check_status(c);
   }
   return NGSLD_OK;  // (the caller's stream: the records are final after ngsld_finish_device)
@@ -293,10 +284,7 @@ namespace eng {
 // during runs only -- include/ngsld.h, BUFFER LIFETIME)
 struct StoreGuard {
   ngsld_ctx *c;
-  ~StoreGuard() {
-    std::unique_lock<std::mutex> lk(c->exact_mu);
-    while (c->exact_state.load() == 1) c->exact_cv.wait_for(lk, std::chrono::milliseconds(1));
-  }
+  ~StoreGuard() { c->store.wait_idle(); }
 };
 
 bool dist_prefix(const ngsld_ctx *c, std::vector<double> &cum, std::vector<uint32_t> &infc) {
@@ -398,7 +386,7 @@ static int drain(ngsld_ctx *c, int rc, std::initializer_list<hipStream_t> stream
 
 static int finish_run(ngsld_ctx *c) {
   bool have = false;  // (the store's builder is still at the sites behind this run's rows: its errors are this run's)
-  if (c->exact_state.load() == 1) RC_TRY(wait_exact_store(c, c->n_sites, &have));
+  if (c->store.building()) RC_TRY(c->store.wait(c, c->n_sites, &have));
   return check_status(c);
 }
 
@@ -577,11 +565,10 @@ struct BatchRun {
     HIP_TRY(c, timed_launch(c, a, st));
     c->slot_dev_applied[k] = false;
     if (replay) {  // (called genotypes: the flagged pairs settled on the device, before anything reads the records)
-      RC_TRY(device_replay(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, k));
+      const ReplayLaunch l{c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, true, k};
+      RC_TRY(device_replay(c, l));
       // (likelihoods: the same once the exact store is there -- a batch issued before that is settled when it is consumed)
-      if (lkl_device_eligible(c) && (exact_store_started(c) || exact_store_is_free(c)))
-        RC_TRY(try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, dev_std[k], dev_ext[k], st, true, k,
-                                     &c->slot_dev_applied[k], exact_sites_needed(c, b.r0, b.r1)));
+      if (lkl_device_ready(c)) RC_TRY(try_device_replay_lkl(c, l, &c->slot_dev_applied[k], exact_sites_needed(c, b.r0, b.r1)));
     }
     // which pairs the kernel flagged for the exact-order replay (counter + list, 32 KB): known to the host with the batch.
     // On the kernel's own stream, right behind it: on the copy stream, behind the records, this small copy took 9 ms per
@@ -631,9 +618,9 @@ struct BatchRun {
   // length, records their copy.
   int settle_late_on_device(int k, const Batch &b, ngsld_rec_std *d_std, ngsld_rec_ext *d_ext, bool &applied) {
     applied = c->slot_dev_applied[k];
-    if (applied || !exact_store_wanted(c, c->h_flags[k].p[0] - c->h_flags[k].p[1])) return NGSLD_OK;
-    RC_TRY(try_device_replay_lkl(c, c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, d_std, d_ext, c->copy_stream, true, k, &applied,
-                                 exact_sites_needed(c, b.r0, b.r1)));
+    if (applied || !c->store.wanted(c, c->h_flags[k].p[0] - c->h_flags[k].p[1])) return NGSLD_OK;
+    const ReplayLaunch l{c->d_flags[k].p, c->flag_cap[k], c->h_row_off[b.r0], b.n, d_std, d_ext, c->copy_stream, true, k};
+    RC_TRY(try_device_replay_lkl(c, l, &applied, exact_sites_needed(c, b.r0, b.r1)));
     return !applied ? NGSLD_OK : send_flag_head(c, c->d_flags[k].p, c->h_flags[k].p, c->flag_cap[k], c->copy_stream, false);
   }
 
@@ -1144,13 +1131,13 @@ int ngsld_run(ngsld_ctx *c, uint64_t s1_begin, uint64_t s1_end, ngsld_sink_fn si
   // group before the run goes batch by batch.
   const uint64_t n_pairs = c->h_row_off[s1_end] - c->h_row_off[s1_begin];
   bool grouped = c->text_mode && c->replay_on && c->h_skip_count * 64ull >= c->n_sites && c->h_skip_count > 0 && lkl_device_eligible(c) &&
-                 !c->exact_failed && (n_pairs >= (1ull << 21) || test_knob("TEXT_GROUP_PAIRS") != nullptr) && !test_knob_is("TEXT_GROUPS", "0");
+                 !c->store.failed() && (n_pairs >= (1ull << 21) || test_knob("TEXT_GROUP_PAIRS") != nullptr) && !test_knob_is("TEXT_GROUPS", "0");
   if (grouped) {
     // The store first -- the matrix is known to be un-called, so it is wanted, and its builder can work beside the first group's
     // kernels -- and then the groups' buffers out of what is left: under a memory cap (ngsld_set_memory_budget) the store must not
     // lose its room to them.  Without the lanes' individual-major copy a group has nothing over a batch: batch by batch then.
-    if (!exact_store_started(c) && !c->exact_failed) RC_TRY(start_exact_store(c));
-    grouped = !c->exact_failed && c->xT_ready.load();
+    RC_TRY(c->store.start(c));  // (idempotent; a store that failed stays failed)
+    grouped = !c->store.failed() && c->store.has_lane_copy();
   }
   if (grouped) {
     uint64_t group_pairs = 1ull << 25;

@@ -297,7 +297,7 @@ def test_a_device_without_room_for_the_store_leaves_the_pairs_to_the_host(eng, m
 
 @pytest.mark.parametrize("callback", [False, True])
 def test_store_built_beside_the_run_in_site_order(eng, monkeypatch, callback):
-    """The exact store is built by a thread of its own while the run that asked for it goes on (engine_replay.hip: exact_builder):
+    """The exact store is built by a thread of its own while the run that asked for it goes on (exact_store.hip: ExactStore::Builder):
     a batch's device-side replay waits only until the builder has passed the batch's last window.  Here the builder is slowed
     and works in chunks of 16 sites, so that every one of the run's many batches -- text rows and records -- catches up with the
     frontier and waits: the records are the host replay's, bit for bit, and the text is the same bytes."""
