@@ -720,6 +720,49 @@ typedef struct {
 int ngsld_linked_pairs(ngsld_ctx *ctx, const ngsld_linked_params *params, const char *const *labels, ngsld_linked_fn sink,
                        void *user, ngsld_linked_stats *stats);
 
+/* ---- LD scan on the device (SCAN.md) ----------------------------------------------------------------------------------------
+ * The TSV this context's plan would print, scanned with a window centred on every site -- without the TSV: the pairs run again
+ * chunk by chunk into device records (every pair kernel, the exact-order replay included) and a kernel adds every counted row
+ * to the windows it is in.  The window of a site c holds the sites of its chromosome within half_window bp of it: an index
+ * range [win_first, win_last]; its left flank is [win_first, c], its right flank [c + 1, win_last].  A row counts iff dist (as
+ * printed) is finite and <= max_kb_dist * 1000, both printed maf >= min_maf, and every chosen field is finite; a counted row
+ * (s1, s2) is in window c iff win_first <= s1 and s2 <= win_last, and there it is LL (s2 <= c), RR (s1 > c) or LR (across c).
+ * Per site: the rows of each class, and per chosen field the sums of |printed ("%f") value| of each class in micro-units
+ * (value * 10^6), zns = the double nearest to the mean over all three classes (Kelly's ZnS), omega = the double nearest to
+ * ((S_LL + S_RR) * n_LR) / ((n_LL + n_RR) * S_LR) (Kim and Nielsen's omega).  The rule and its refusals are in SCAN.md.  Both
+ * structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_scan_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (default) */
+  uint64_t half_window;       /* H: a window reaches H bp to either side of its site, 0 <= H < 2^31 */
+  double max_kb_dist;         /* a row needs dist <= max_kb_dist * 1000 (INFINITY: no limit, the default) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  uint64_t reserved;          /* 0 */
+} ngsld_scan_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_scan_stats) */
+  uint32_t reserved;          /* 0 */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows that count (in a window or not) */
+  uint64_t largest_window;    /* sites of the largest window */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, scan_ms, total_ms;  /* pair kernels + replay, the scan kernel and the prefix sums (kernel time), the whole call */
+} ngsld_scan_stats;
+
+/* The scan after ngsld_plan; the context keeps it until the next ngsld_scan, ngsld_plan or ngsld_set_*.  stats may be NULL.
+ * NGSLD_ERR_INVALID for a plan whose distance window (ngsld_params.max_kb_dist > 0) is below 2 * half_window bp: a window would
+ * hold site pairs the table never had.  NGSLD_ERR_UNSUPPORTED for non-integer position gaps (the windows come from the
+ * positions' prefix sums), a value of 2^38 micro-units or more (|x| >= 274877.906944, naming the pair), or a window whose sum
+ * could pass 2^63 micro-units. */
+int ngsld_scan(ngsld_ctx *ctx, const ngsld_scan_params *params, ngsld_scan_stats *stats);
+/* The last ngsld_scan's arrays, n_sites entries each, any pointer may be NULL: win_first[] and win_last[] (site indices), the
+ * rows n_ll[], n_rr[], n_lr[] (the same for every field), and of one chosen statistic (field = TSV column 4..7) the sums
+ * sum_ll[], sum_rr[], sum_lr[] in micro-units, zns[] (NaN where the window has no row) and omega[] (NaN where n_ll + n_rr,
+ * n_lr or sum_lr is 0). */
+int ngsld_scan_get(ngsld_ctx *ctx, int field, uint32_t *win_first, uint32_t *win_last, uint64_t *n_ll, uint64_t *n_rr,
+                   uint64_t *n_lr, int64_t *sum_ll, int64_t *sum_rr, int64_t *sum_lr, double *zns, double *omega);
+
 #ifdef __cplusplus
 }
 #endif

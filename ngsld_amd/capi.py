@@ -100,6 +100,7 @@ SYMBOLS = [
     "ngsld_clusters", "ngsld_clusters_sites", "ngsld_clusters_table",
     "ngsld_grid", "ngsld_grid_cells", "ngsld_grid_chromosomes", "ngsld_grid_get",
     "ngsld_linked_pairs",
+    "ngsld_scan", "ngsld_scan_get",
 ]
 
 
@@ -197,6 +198,19 @@ class LinkedParams(C.Structure):
     """ngsld_linked_params (include/ngsld.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("min_weight", C.c_double), ("max_kb_dist", C.c_double),
                 ("min_maf", C.c_double), ("abs_value", C.c_int32), ("want", C.c_int32)]
+
+
+class ScanParams(C.Structure):
+    """ngsld_scan_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("half_window", C.c_uint64), ("max_kb_dist", C.c_double),
+                ("min_maf", C.c_double), ("reserved", C.c_uint64)]
+
+
+class ScanStats(C.Structure):
+    """ngsld_scan_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("largest_window", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("scan_ms", C.c_double),
+                ("total_ms", C.c_double)]
 
 
 class LinkedBatch(C.Structure):
@@ -363,6 +377,9 @@ def lib() -> C.CDLL:
             L.ngsld_grid_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
         if hasattr(L, "ngsld_linked_pairs"):
             L.ngsld_linked_pairs.argtypes = [vp, C.POINTER(LinkedParams), C.POINTER(C.c_char_p), LINKED_FN, vp, C.POINTER(LinkedStats)]
+        if hasattr(L, "ngsld_scan"):
+            L.ngsld_scan.argtypes = [vp, C.POINTER(ScanParams), C.POINTER(ScanStats)]
+            L.ngsld_scan_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1149,6 +1166,41 @@ class Engine:
                                                   sites[f"mean_{f}"].ctypes.data))
         sites = {k: v[:self.n_sites] for k, v in sites.items()}
         return sites, {k: getattr(st, k) for k, _ in SiteLdStats._fields_ if k != "struct_size"}
+
+    def scan(self, half_window: int, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0) -> tuple[dict, dict]:
+        """The LD scan of the planned pairs on the device (ngsld_scan, SCAN.md): (windows, stats).  windows holds numpy arrays
+        of n_sites entries: "win_first" and "win_last" (uint32: the window of a site as a range of site indices), "n_ll", "n_rr",
+        "n_lr" (the rows inside the left flank, inside the right flank and across the site) and per statistic F of ld (r2_ExpG,
+        D, Dp, r2) "sum_ll_F", "sum_rr_F", "sum_lr_F" (int64 micro-units: |value| * 10^6), "zns_F" and "omega_F" (NaN where
+        they are not defined)."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        if not 0 <= int(half_window) < 2 ** 64:
+            raise ValueError("half_window must be a non-negative integer")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        p = ScanParams(C.sizeof(ScanParams), mask, int(half_window), float(max_kb_dist), float(min_maf), 0)
+        st = ScanStats()
+        st.struct_size = C.sizeof(ScanStats)
+        self._check(self._L.ngsld_scan(self._h, C.byref(p), C.byref(st)))
+        m = max(self.n_sites, 1)
+        win = {"win_first": np.zeros(m, dtype=np.uint32), "win_last": np.zeros(m, dtype=np.uint32)}
+        for cl in ("ll", "rr", "lr"):
+            win[f"n_{cl}"] = np.zeros(m, dtype=np.uint64)
+        for k, f in enumerate(DECAY_FIELDS):
+            if not (mask >> k) & 1:
+                continue
+            for cl in ("ll", "rr", "lr"):
+                win[f"sum_{cl}_{f}"] = np.zeros(m, dtype=np.int64)
+            win[f"zns_{f}"], win[f"omega_{f}"] = np.zeros(m), np.zeros(m)
+            self._check(self._L.ngsld_scan_get(self._h, 4 + k, win["win_first"].ctypes.data, win["win_last"].ctypes.data,
+                                               win["n_ll"].ctypes.data, win["n_rr"].ctypes.data, win["n_lr"].ctypes.data,
+                                               win[f"sum_ll_{f}"].ctypes.data, win[f"sum_rr_{f}"].ctypes.data,
+                                               win[f"sum_lr_{f}"].ctypes.data, win[f"zns_{f}"].ctypes.data,
+                                               win[f"omega_{f}"].ctypes.data))
+        win = {k: v[:self.n_sites] for k, v in win.items()}
+        return win, {k: getattr(st, k) for k, _ in ScanStats._fields_ if k not in ("struct_size", "reserved")}
 
     def clusters(self, field: int = 7, min_weight: float = 0.5, max_kb_dist: float = float("inf"), min_maf: float = 0.0,
                  abs_value: bool = True, min_size: int = 2) -> tuple[np.ndarray, dict, dict]:

@@ -28,6 +28,9 @@
 //   * --linked_out FILE / --linked_outH FILE (new) and the other --linked_* flags: the rows of the table at or above an LD floor,
 //     each as the table prints it and in the table's order, compacted on the device (ngsld_linked_pairs, LINKED.md); taken out
 //     of argv the same way, no TSV without --out; a name ending in .gz is written gzip-compressed;
+//   * --scan_out FILE --scan_half_window H (new) and the other --scan_* flags: a window of H bp to either side of every site --
+//     the rows inside its two flanks and across the site, Kelly's ZnS and Kim and Nielsen's omega -- summed on the device
+//     (ngsld_scan, SCAN.md); taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -174,6 +177,13 @@ struct LinkedArgs {
   bool is_signed = false;
   ngsld_linked_params p{};
 } linked;
+
+// ---- --scan_* (new): the LD scan on the device ----
+struct ScanArgs {
+  bool given = false;  // any --scan_* flag
+  const char *out = nullptr, *half_window = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr;
+  ngsld_scan_params p{};
+} scan;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -433,6 +443,31 @@ void check_linked_args(const Params &pars) {
   one_device(__FUNCTION__, pars, "--linked_out");
 }
 
+void check_scan_args(const Params &pars) {
+  ScanArgs *sa = &scan;
+  if (sa->out == nullptr) error(__FUNCTION__, "the --scan_* options need --scan_out FILE!");
+  if (*sa->out == 0) error(__FUNCTION__, "--scan_out needs a file name!");
+  ngsld_scan_params &p = sa->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  if (sa->half_window == nullptr) error(__FUNCTION__, "--scan_out needs the half window in bp: --scan_half_window INT!");
+  if (!parse_position(sa->half_window, &p.half_window) || p.half_window >= (1ull << 31))
+    error(__FUNCTION__, "--scan_half_window must be an integer in [0, 2147483647]!");
+  ld_arg(__FUNCTION__, "--scan_ld", sa->ld, &p.fields);
+  dist_arg(__FUNCTION__, "--scan_max_kb_dist", sa->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--scan_min_maf", sa->min_maf, &p.min_maf);
+  // (the library refuses it too: here before a device is touched)
+  if (pars.max_kb_dist > 0 && pars.max_kb_dist * 1000 < 2 * p.half_window) {
+    const std::string msg = "--scan_half_window " + std::to_string(p.half_window) + " needs the pairs up to " +
+                            std::to_string(2 * p.half_window) + " bp apart: --max_kb_dist holds them up to " +
+                            std::to_string(pars.max_kb_dist * 1000) + " bp!";
+    error(__FUNCTION__, msg.c_str());
+  }
+  one_device(__FUNCTION__, pars, "--scan_out");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -558,6 +593,57 @@ void run_site(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
   if (pars.verbose >= 1)
     fprintf(stderr, "==> Site LD: %lu of %lu sites in %lu of %lu pairs\n", (unsigned long)st.sites_with_pairs, (unsigned long)n,
             (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
+}
+
+// one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the sites of
+// its window and of its two flanks, the rows inside the left flank, inside the right flank and across the site, then per chosen
+// statistic the three sums, zns and omega; NA where a ratio is not defined
+void run_scan(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  ScanArgs &sa = scan;
+  ngsld_scan_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_scan(ctx, &sa.p, &st) != NGSLD_OK) error("ngsld_scan", ngsld_last_error(ctx));
+  const uint64_t n = pars.n_sites;
+  const std::vector<int> fields = fields_of(sa.p.fields);
+  const size_t nf = fields.size();
+  std::vector<uint32_t> first(n), last(n);
+  std::vector<uint64_t> rows(3 * n);
+  std::vector<int64_t> sum(nf * 3 * n);
+  std::vector<double> zns(nf * n), omega(nf * n);
+  for (size_t v = 0; v < nf; ++v)
+    if (ngsld_scan_get(ctx, 4 + fields[v], first.data(), last.data(), rows.data(), rows.data() + n, rows.data() + 2 * n,
+                       sum.data() + (v * 3) * n, sum.data() + (v * 3 + 1) * n, sum.data() + (v * 3 + 2) * n, zns.data() + v * n,
+                       omega.data() + v * n) != NGSLD_OK)
+      error("ngsld_scan_get", ngsld_last_error(ctx));
+  FILE *f = fopen(sa.out, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open LD scan output file!");
+  fprintf(f, "site\twin_sites\tleft_sites\tright_sites\tn_ll\tn_rr\tn_lr");
+  for (int k : fields)
+    fprintf(f, "\tsum_ll_%s\tsum_rr_%s\tsum_lr_%s\tzns_%s\tomega_%s", kDecayFields[k], kDecayFields[k], kDecayFields[k], kDecayFields[k],
+            kDecayFields[k]);
+  fprintf(f, "\n");
+  uint64_t with_rows = 0;
+  for (uint64_t s = 0; s < n; ++s) {
+    print_site(f, pos, s);
+    fprintf(f, "\t%lu\t%lu\t%lu\t%lu\t%lu\t%lu", (unsigned long)(last[s] - first[s] + 1), (unsigned long)(s - first[s] + 1),
+            (unsigned long)(last[s] - s), (unsigned long)rows[s], (unsigned long)rows[n + s], (unsigned long)rows[2 * n + s]);
+    if (rows[s] + rows[n + s] + rows[2 * n + s] > 0) ++with_rows;
+    for (size_t v = 0; v < nf; ++v) {
+      for (size_t k = 0; k < 3; ++k) print_micro(f, sum[(v * 3 + k) * n + s]);
+      for (const double x : {zns[v * n + s], omega[v * n + s]}) {
+        if (std::isnan(x))
+          fprintf(f, "\tNA");
+        else
+          fprintf(f, "\t%.17g", x);
+      }
+    }
+    fprintf(f, "\n");
+  }
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD scan output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD scan: %lu of %lu windows with rows (the largest of %lu sites), %lu of %lu pairs counted\n",
+            (unsigned long)with_rows, (unsigned long)n, (unsigned long)st.largest_window, (unsigned long)st.pairs_counted,
+            (unsigned long)st.pairs);
 }
 
 // one line per cell with rows, by chromosome (file order), bin1, bin2: the chromosome, the lower breaks b * B of the two
@@ -823,6 +909,10 @@ const Family kFamilies[] = {
      {{"linked_out", &linked.out}, {"linked_outH", &linked.outH}, {"linked_field", &linked.field},
       {"linked_min_weight", &linked.min_weight}, {"linked_max_kb_dist", &linked.max_kb_dist}, {"linked_min_maf", &linked.min_maf}},
      "linked_signed", &linked.is_signed, &linked.given, check_linked_args, run_linked, "linked pairs"},  // (a pass of its own)
+    {"scan_",
+     {{"scan_out", &scan.out}, {"scan_half_window", &scan.half_window}, {"scan_ld", &scan.ld}, {"scan_max_kb_dist", &scan.max_kb_dist},
+      {"scan_min_maf", &scan.min_maf}},
+     nullptr, nullptr, &scan.given, check_scan_args, run_scan, "LD scan"},  // (a pass of its own)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1289,7 +1379,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----

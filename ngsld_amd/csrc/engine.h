@@ -486,6 +486,18 @@ struct ngsld_ctx {
   } grid;
   void clear_grid() { grid = Grid(); }
 
+  // the windows of the last ngsld_scan (scan.hip), until the next ngsld_scan, ngsld_plan or ngsld_set_* (cleared with the block
+  // matrices): per site its window and the rows of the three classes, and per chosen field [rank][class LL, RR, LR][site] the
+  // sums in micro-units, then [rank][site] zns and omega
+  struct Scan {
+    uint32_t fields = 0;
+    std::vector<uint32_t> first, last;
+    std::vector<uint64_t> n;  // [class][site]
+    std::vector<int64_t> sum;
+    std::vector<double> zns, omega;
+  } scan;
+  void clear_scan() { scan = Scan(); }
+
   // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
   // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
   uint32_t blocks_fields = 0;
@@ -501,6 +513,7 @@ struct ngsld_ctx {
     clear_sites();
     clear_clusters();
     clear_grid();
+    clear_scan();
     blocks_fields = 0;
     blocks_members = 0;
     d_blocks_val.release();

@@ -16,10 +16,12 @@
 //   EXACT_CHUNK_SITES, EXACT_SLOW_US, EXACT_STORE_NO_ROOM, REPLAY_LIST_CAP, REPLAY_SOURCE, LANE_ITER_CAP,
 //   PRUNE_HOST_AFTER, DECAY_LDS_BYTES, DECAY_CHUNK_PAIRS, BLOCKS_CHUNK_PAIRS, BLOCKS_HOST_ROWS, BLOCKS_TEXT_ROWS,
 //   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS, GRID_LDS_BYTES, GRID_CHUNK_PAIRS,
-//   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST,
+//   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST, SCAN_CHUNK_PAIRS, SCAN_PLANT_DP,
 //   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT,
 //   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS
 // LINKED_FORCE_HOST=1: every chunk of ngsld_linked_pairs takes the host formatter, as BLOCKS_HOST_ROWS does for the block matrices.
+// SCAN_PLANT_DP=R:X: record R of the plan gets D' = X in ngsld_scan's record buffer before its kernel reads it (scan.hip) -- no input
+// gives a finite D' near 2^38 micro-units, and the refusal of one has to be reached somehow.
 // PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS and SUM_WRAP_LIMIT bring the large-job paths of the record passes (record_pass.h) down to jobs of a few thousand pairs, where
 // tests/test_gpu_record_pass_large.py holds them to the passes' rules: ngsld_prune's chunk loop (its edge arrays regrown and its
 // edge count carried from chunk to chunk; a row that does not fit the record buffer), a chunk's items cut into several launches

@@ -1,6 +1,6 @@
 // ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
 // (site_ld.hip), of ngsld_clusters' clusters (cluster.hip) and of ngsld_grid's cells (grid.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
-// compiles it alone.
+// compiles it alone.  ngsld_scan's omega (scan.hip) is a ratio of two such products, rounded once by ratio_nearest.
 #pragma once
 
 #include <stdint.h>
@@ -31,6 +31,40 @@ inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
   sticky = sticky || (low & 1);
   if ((low & 2) && (sticky || (m & 1))) ++m;
   return std::ldexp((double)m, 2 - sh);
+}
+
+// the double nearest to num / den (round half to even) for any num < 2^128 and 0 < den < 2^127, whatever the quotient: ngsld_scan's
+// omega (scan.hip) is a ratio of two products of a sum and a count, which can lie far beyond the 2^54 of div_nearest and far
+// below 1.  Where both operands are below 2^53 they are doubles, and one IEEE division is that one rounding.  Elsewhere the
+// integer quotient is cut down to, or carried on by long division up to, 55 significant bits: 53 of the result, the round bit and
+// one more that joins the sticky remainder.  tests/test_ratio_nearest.py holds both branches to the exact quotient.
+inline double ratio_nearest(unsigned __int128 num, unsigned __int128 den) {
+  if (num == 0) return 0.0;
+  if (num < ((unsigned __int128)1 << 53) && den < ((unsigned __int128)1 << 53)) return (double)(uint64_t)num / (double)(uint64_t)den;
+  unsigned __int128 q = num / den, r = num % den;
+  int e = 0;  // num / den = (q + (what was cut off)) * 2^e
+  bool sticky = false;
+  while (q >= ((unsigned __int128)1 << 55)) {
+    sticky = sticky || (q & 1);
+    q >>= 1;
+    ++e;
+  }
+  if (e == 0)
+    while (q < ((unsigned __int128)1 << 54)) {
+      r <<= 1;
+      q <<= 1;
+      if (r >= den) {
+        r -= den;
+        q |= 1;
+      }
+      --e;
+    }
+  sticky = sticky || r != 0;
+  const unsigned low = (unsigned)(q & 3);
+  uint64_t m = (uint64_t)(q >> 2);
+  sticky = sticky || (low & 1);
+  if ((low & 2) && (sticky || (m & 1))) ++m;
+  return std::ldexp((double)m, e + 2);
 }
 
 // the double nearest to sum / (10^6 * rows): the mean of `rows` printed values whose micro-units add up to `sum` (ngsld_grid's

@@ -1,8 +1,10 @@
 // record_pass.h -- the host frame of the record passes: ngsld_prune (prune.hip), ngsld_decay (decay.hip), ngsld_blocks
-// (blocks.hip), ngsld_site_ld (site_ld.hip), ngsld_clusters (cluster.hip), ngsld_grid (grid.hip) and ngsld_linked_pairs (linked.hip) read the records of rows chunk
+// (blocks.hip), ngsld_site_ld (site_ld.hip), ngsld_clusters (cluster.hip), ngsld_grid (grid.hip), ngsld_linked_pairs (linked.hip)
+// and ngsld_scan (scan.hip) read the records of rows chunk
 // by chunk and run a kernel of their own over each chunk's items (ld_records.h).  What they share on the host is here, once: the
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
 // linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ.
+// (ngsld_scan uses the site filter, the chunk loop, the two refusals and the guard of the sums.)
 // Host code; the definitions are in record_pass.hip.
 #pragma once
 
