@@ -763,6 +763,41 @@ int ngsld_scan(ngsld_ctx *ctx, const ngsld_scan_params *params, ngsld_scan_stats
 int ngsld_scan_get(ngsld_ctx *ctx, int field, uint32_t *win_first, uint32_t *win_last, uint64_t *n_ll, uint64_t *n_rr,
                    uint64_t *n_lr, int64_t *sum_ll, int64_t *sum_rr, int64_t *sum_lr, double *zns, double *omega);
 
+/* ---- several analyses over one run of the pair kernels ----
+ * ngsld_prune, ngsld_decay, ngsld_site_ld, ngsld_clusters, ngsld_grid and ngsld_scan each run every planned pair through the pair
+ * kernels.  ngsld_analyze runs the pairs once, chunk of rows by chunk, and every listed analysis reads each chunk's records in
+ * list order; the results are the single calls' bit for bit and are read through the single calls' getters (pruning's through
+ * site_state).  ANALYZE.md has the rule.  ngsld_blocks and ngsld_linked_pairs stay calls of their own. */
+enum { NGSLD_AN_PRUNE = 1, NGSLD_AN_DECAY, NGSLD_AN_SITE_LD, NGSLD_AN_CLUSTERS, NGSLD_AN_GRID, NGSLD_AN_SCAN };
+
+typedef struct ngsld_analysis {
+  uint32_t struct_size;         /* sizeof(ngsld_analysis) */
+  uint32_t kind;                /* NGSLD_AN_* */
+  const void *params;           /* the kind's own ngsld_*_params */
+  void *stats;                  /* the kind's own ngsld_*_stats, filled as by its single call (pairs_ms is the shared figure); may be NULL */
+  const char *const *labels;    /* prune, grid: as in the single call; NULL otherwise */
+  uint8_t *site_state;          /* prune: as in ngsld_prune; NULL otherwise */
+} ngsld_analysis;
+
+typedef struct ngsld_analyze_stats {
+  uint32_t struct_size;         /* sizeof(ngsld_analyze_stats) */
+  uint32_t n_analyses;          /* the length of the list */
+  uint64_t pairs;               /* planned pairs */
+  uint64_t pairs_run;           /* pairs handed to the pair kernels in this call: == pairs says they ran once (0 after a refusal
+                                   made before they start, and when no listed analysis has anything to read) */
+  uint64_t chunks;              /* chunks of rows the pairs ran in */
+  double pairs_ms, kernels_ms, total_ms;  /* pair kernels + replay (shared), the analyses' kernels over the chunks, the whole call */
+} ngsld_analyze_stats;
+
+/* After ngsld_plan.  Before any device work: NGSLD_ERR_INVALID for n == 0, an unknown kind, a kind listed twice (a context keeps
+ * one result per kind) or a wrong struct_size, and every entry's parameters are checked with its single call's code and message.
+ * The stores of the listed kinds are emptied on entry; on any failure -- a refusal that a single call would make, with its
+ * message, at whatever chunk it arrives -- every listed store is left empty and the context stays usable; kinds not listed keep
+ * what they held.  The chunk is that of the single calls (2^24 records): with pruning listed a row longer than the chunk is
+ * refused as by ngsld_prune, without it the buffer fits the longest row.  All listed analyses hold their device state at once.
+ * stats may be NULL. */
+int ngsld_analyze(ngsld_ctx *ctx, ngsld_analysis *list, uint32_t n, ngsld_analyze_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

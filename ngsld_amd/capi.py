@@ -101,6 +101,7 @@ SYMBOLS = [
     "ngsld_grid", "ngsld_grid_cells", "ngsld_grid_chromosomes", "ngsld_grid_get",
     "ngsld_linked_pairs",
     "ngsld_scan", "ngsld_scan_get",
+    "ngsld_analyze",
 ]
 
 
@@ -211,6 +212,38 @@ class ScanStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
                 ("largest_window", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("scan_ms", C.c_double),
                 ("total_ms", C.c_double)]
+
+
+class Analysis(C.Structure):
+    """ngsld_analysis (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("params", C.c_void_p), ("stats", C.c_void_p),
+                ("labels", C.POINTER(C.c_char_p)), ("site_state", C.c_void_p)]
+
+
+class AnalyzeStats(C.Structure):
+    """ngsld_analyze_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_analyses", C.c_uint32), ("pairs", C.c_uint64), ("pairs_run", C.c_uint64),
+                ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("kernels_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+# ngsld_analysis.kind, in the order of Engine.analyze's arguments
+AN_PRUNE, AN_DECAY, AN_SITE_LD, AN_CLUSTERS, AN_GRID, AN_SCAN = 1, 2, 3, 4, 5, 6
+ANALYSES = {"prune": AN_PRUNE, "decay": AN_DECAY, "site_ld": AN_SITE_LD, "clusters": AN_CLUSTERS, "grid": AN_GRID,
+            "scan": AN_SCAN}
+
+
+class _Job:
+    """One analysis between its arguments and its result: the structs of its call (kept alive here), the single call, and
+    read(), which fetches the result through the getters.  Engine.prune ... Engine.scan run call() then read(); Engine.analyze
+    lists several jobs in one ngsld_analyze and reads each."""
+
+    def __init__(self, kind, params, stats, call, read, labels=None, site_state=None):
+        self.kind, self.params, self.stats, self.call, self.read = kind, params, stats, call, read
+        self.labels, self.site_state = labels, site_state
+
+    def run(self):
+        self.call()
+        return self.read()
 
 
 class LinkedBatch(C.Structure):
@@ -377,6 +410,8 @@ def lib() -> C.CDLL:
             L.ngsld_grid_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
         if hasattr(L, "ngsld_linked_pairs"):
             L.ngsld_linked_pairs.argtypes = [vp, C.POINTER(LinkedParams), C.POINTER(C.c_char_p), LINKED_FN, vp, C.POINTER(LinkedStats)]
+        if hasattr(L, "ngsld_analyze"):
+            L.ngsld_analyze.argtypes = [vp, C.POINTER(Analysis), C.c_uint32, C.POINTER(AnalyzeStats)]
         if hasattr(L, "ngsld_scan"):
             L.ngsld_scan.argtypes = [vp, C.POINTER(ScanParams), C.POINTER(ScanStats)]
             L.ngsld_scan_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1104,6 +1139,11 @@ class Engine:
               precision: int = 4) -> tuple[np.ndarray, dict]:
         """LD pruning of the planned pairs on the device (ngsld_prune): (site_state, stats) -- site_state[s] is 0 (not a node),
         1 (kept) or 2 (excluded); labels None = every label "(null)"."""
+        return self._prune_job(labels, field, max_kb_dist, min_weight, weight_type, keep_heavy, subset, precision).run()
+
+    def _prune_job(self, labels: list[str] | None, field: int = 7, max_kb_dist: float = float("inf"), min_weight: float = 0.0,
+                   weight_type: str = "a", keep_heavy: bool = False, subset: list[str] | None = None,
+                   precision: int = 4) -> _Job:
         arr = None if labels is None else (C.c_char_p * len(labels))(*[l.encode() for l in labels])
         sub = None if subset is None else (C.c_char_p * max(len(subset), 1))(*[l.encode() for l in subset])
         p = PruneParams(C.sizeof(PruneParams), field, float(max_kb_dist), float(min_weight), ord(weight_type), int(keep_heavy),
@@ -1111,13 +1151,24 @@ class Engine:
         st = PruneStats()
         st.struct_size = C.sizeof(PruneStats)
         state = np.zeros(max(self.n_sites, 1), dtype=np.uint8)
-        self._check(self._L.ngsld_prune(self._h, C.byref(p), arr, state.ctypes.data, C.byref(st)))
-        return state[:self.n_sites], {k: getattr(st, k) for k, _ in PruneStats._fields_ if k not in ("struct_size", "reserved")}
+
+        def call():
+            self._check(self._L.ngsld_prune(self._h, C.byref(p), arr, state.ctypes.data, C.byref(st)))
+
+        def read():
+            return state[:self.n_sites], {k: getattr(st, k) for k, _ in PruneStats._fields_ if k not in ("struct_size", "reserved")}
+
+        job = _Job(AN_PRUNE, p, st, call, read, labels=arr, site_state=state)
+        job.keep = sub  # (the params point into it)
+        return job
 
     def decay(self, ld=("r2",), bin_size: float = 250, max_kb_dist: float = float("inf"),
               min_maf: float = 0.0) -> tuple[dict, dict]:
         """LD decay bins of the planned pairs on the device (ngsld_decay): (bins, stats).  bins holds numpy arrays "dist" (each
         non-empty bin's lower break), "n" (rows) and one mean per statistic of ld (r2_ExpG, D, Dp, r2)."""
+        return self._decay_job(ld, bin_size, max_kb_dist, min_maf).run()
+
+    def _decay_job(self, ld=("r2",), bin_size: float = 250, max_kb_dist: float = float("inf"), min_maf: float = 0.0) -> _Job:
         ld = (ld,) if isinstance(ld, str) else tuple(ld)
         bad = [f for f in ld if f not in DECAY_FIELDS]
         if bad or not ld:
@@ -1127,7 +1178,13 @@ class Engine:
         p = DecayParams(C.sizeof(DecayParams), mask, float(bin_size), float(max_kb_dist), float(min_maf))
         st = DecayStats()
         st.struct_size = C.sizeof(DecayStats)
-        self._check(self._L.ngsld_decay(self._h, C.byref(p), C.byref(st)))
+
+        def call():
+            self._check(self._L.ngsld_decay(self._h, C.byref(p), C.byref(st)))
+
+        return _Job(AN_DECAY, p, st, call, lambda: self._decay_read(st, names))
+
+    def _decay_read(self, st, names) -> tuple[dict, dict]:
         nb = st.bins
         dist = np.zeros(max(nb, 1))
         cnt = np.zeros(max(nb, 1), dtype=np.uint64)
@@ -1145,6 +1202,10 @@ class Engine:
         """Per-site LD summaries of the planned pairs on the device (ngsld_site_ld, SITES.md): (sites, stats).  sites holds
         numpy arrays of n_sites entries: "n" (counted rows) and per statistic F of ld (r2_ExpG, D, Dp, r2) "sum_F" and "max_F"
         (int64 micro-units: value * 10^6), "linked_F" and "mean_F".  Where n is 0, max_F is the smallest int64 and mean_F NaN."""
+        return self._site_ld_job(ld, max_kb_dist, min_maf, linked_min, abs_value).run()
+
+    def _site_ld_job(self, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0, linked_min: float = 0.5,
+                     abs_value: bool = True) -> _Job:
         ld = (ld,) if isinstance(ld, str) else tuple(ld)
         bad = [f for f in ld if f not in DECAY_FIELDS]
         if bad or not ld:
@@ -1153,7 +1214,13 @@ class Engine:
         p = SiteLdParams(C.sizeof(SiteLdParams), mask, float(max_kb_dist), float(min_maf), float(linked_min), int(bool(abs_value)), 0)
         st = SiteLdStats()
         st.struct_size = C.sizeof(SiteLdStats)
-        self._check(self._L.ngsld_site_ld(self._h, C.byref(p), C.byref(st)))
+
+        def call():
+            self._check(self._L.ngsld_site_ld(self._h, C.byref(p), C.byref(st)))
+
+        return _Job(AN_SITE_LD, p, st, call, lambda: self._site_ld_read(st, mask))
+
+    def _site_ld_read(self, st, mask) -> tuple[dict, dict]:
         m = max(self.n_sites, 1)
         sites = {"n": np.zeros(m, dtype=np.uint64)}
         for k, f in enumerate(DECAY_FIELDS):
@@ -1173,6 +1240,9 @@ class Engine:
         "n_lr" (the rows inside the left flank, inside the right flank and across the site) and per statistic F of ld (r2_ExpG,
         D, Dp, r2) "sum_ll_F", "sum_rr_F", "sum_lr_F" (int64 micro-units: |value| * 10^6), "zns_F" and "omega_F" (NaN where
         they are not defined)."""
+        return self._scan_job(half_window, ld, max_kb_dist, min_maf).run()
+
+    def _scan_job(self, half_window: int, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0) -> _Job:
         ld = (ld,) if isinstance(ld, str) else tuple(ld)
         bad = [f for f in ld if f not in DECAY_FIELDS]
         if bad or not ld:
@@ -1183,7 +1253,13 @@ class Engine:
         p = ScanParams(C.sizeof(ScanParams), mask, int(half_window), float(max_kb_dist), float(min_maf), 0)
         st = ScanStats()
         st.struct_size = C.sizeof(ScanStats)
-        self._check(self._L.ngsld_scan(self._h, C.byref(p), C.byref(st)))
+
+        def call():
+            self._check(self._L.ngsld_scan(self._h, C.byref(p), C.byref(st)))
+
+        return _Job(AN_SCAN, p, st, call, lambda: self._scan_read(st, mask))
+
+    def _scan_read(self, st, mask) -> tuple[dict, dict]:
         m = max(self.n_sites, 1)
         win = {"win_first": np.zeros(m, dtype=np.uint32), "win_last": np.zeros(m, dtype=np.uint32)}
         for cl in ("ll", "rr", "lr"):
@@ -1208,11 +1284,21 @@ class Engine:
         cluster_ids holds every site's cluster (uint32; 0: not a node; ids count singletons too).  table holds numpy arrays with
         one entry per cluster of at least min_size sites, in id order: "id", "size", "first", "last", "span", "edges", "sum"
         (int64 micro-units: value * 10^6), "mean" (NaN without edges) and "density" (NaN for a singleton)."""
+        return self._clusters_job(field, min_weight, max_kb_dist, min_maf, abs_value, min_size).run()
+
+    def _clusters_job(self, field: int = 7, min_weight: float = 0.5, max_kb_dist: float = float("inf"), min_maf: float = 0.0,
+                      abs_value: bool = True, min_size: int = 2) -> _Job:
         p = ClustersParams(C.sizeof(ClustersParams), int(field), float(max_kb_dist), float(min_maf), float(min_weight),
                            int(bool(abs_value)), 0)
         st = ClustersStats()
         st.struct_size = C.sizeof(ClustersStats)
-        self._check(self._L.ngsld_clusters(self._h, C.byref(p), C.byref(st)))
+
+        def call():
+            self._check(self._L.ngsld_clusters(self._h, C.byref(p), C.byref(st)))
+
+        return _Job(AN_CLUSTERS, p, st, call, lambda: self._clusters_read(st, min_size))
+
+    def _clusters_read(self, st, min_size) -> tuple[np.ndarray, dict, dict]:
         ids = np.zeros(max(self.n_sites, 1), dtype=np.uint32)
         self._check(self._L.ngsld_clusters_sites(self._h, ids.ctypes.data))
         rows = C.c_uint64(0)
@@ -1233,6 +1319,10 @@ class Engine:
         "bin2" (the lower breaks b * bin_size of the windows of the pair's first and second site, as --grid_out writes them), "n"
         (counted rows) and per statistic F of ld (r2_ExpG, D, Dp, r2) "sum_F" and "max_F" (int64 micro-units: value * 10^6),
         "linked_F" and "mean_F"."""
+        return self._grid_job(labels, bin_size, ld, max_kb_dist, min_maf, linked_min, abs_value).run()
+
+    def _grid_job(self, labels: list[str] | None, bin_size: int, ld=("r2",), max_kb_dist: float = float("inf"),
+                  min_maf: float = 0.0, linked_min: float = 0.5, abs_value: bool = True) -> _Job:
         ld = (ld,) if isinstance(ld, str) else tuple(ld)
         bad = [f for f in ld if f not in DECAY_FIELDS]
         if bad or not ld:
@@ -1243,7 +1333,13 @@ class Engine:
                        int(bool(abs_value)), 0)
         st = GridStats()
         st.struct_size = C.sizeof(GridStats)
-        self._check(self._L.ngsld_grid(self._h, C.byref(p), arr, C.byref(st)))
+
+        def call():
+            self._check(self._L.ngsld_grid(self._h, C.byref(p), arr, C.byref(st)))
+
+        return _Job(AN_GRID, p, st, call, lambda: self._grid_read(st, mask, bin_size), labels=arr)
+
+    def _grid_read(self, st, mask, bin_size) -> tuple[dict, dict]:
         nc = int(st.cells)
         m = max(nc, 1)
         n_chr = C.c_uint64(0)
@@ -1267,6 +1363,28 @@ class Engine:
                                                cells[f"linked_{f}"].ctypes.data, cells[f"mean_{f}"].ctypes.data))
         cells = {k: v[:nc] for k, v in cells.items()}
         return cells, {k: getattr(st, k) for k, _ in GridStats._fields_ if k != "struct_size"}
+
+    def analyze(self, prune: dict | None = None, decay: dict | None = None, site_ld: dict | None = None,
+                clusters: dict | None = None, grid: dict | None = None, scan: dict | None = None) -> tuple[dict, dict]:
+        """Several analyses over one run of the pair kernels (ngsld_analyze, ANALYZE.md): (results, stats).  Each argument is a
+        dict of the keyword arguments of the method of that name (None: not asked for); results[name] is exactly what that
+        method returns.  The list goes to the library in the order of this signature."""
+        asked = [("prune", prune), ("decay", decay), ("site_ld", site_ld), ("clusters", clusters), ("grid", grid), ("scan", scan)]
+        jobs = {name: getattr(self, f"_{name}_job")(**kw) for name, kw in asked if kw is not None}
+        arr = (Analysis * max(len(jobs), 1))()
+        for a, job in zip(arr, jobs.values()):
+            a.struct_size, a.kind = C.sizeof(Analysis), job.kind
+            a.params, a.stats = C.addressof(job.params), C.addressof(job.stats)
+            if job.labels is not None:
+                a.labels = C.cast(job.labels, C.POINTER(C.c_char_p))
+            if job.site_state is not None:
+                a.site_state = job.site_state.ctypes.data
+        st = AnalyzeStats()
+        st.struct_size = C.sizeof(AnalyzeStats)
+        self.analyze_stats = st  # (what a refused call reports: pairs_run stays 0 when the pair kernels never started)
+        self._check(self._L.ngsld_analyze(self._h, arr, len(jobs), C.byref(st)))
+        results = {name: job.read() for name, job in jobs.items()}
+        return results, {k: getattr(st, k) for k, _ in AnalyzeStats._fields_ if k != "struct_size"}
 
     def linked_pairs(self, labels: list[str] | None = None, field: int = 7, min_weight: float = 0.5, abs_value: bool = True,
                      max_kb_dist: float = float("inf"), min_maf: float = 0.0, records: bool = True, text: bool = False,

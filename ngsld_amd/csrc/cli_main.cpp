@@ -126,6 +126,10 @@ struct PruneArgs {
   bool keep_heavy = false;
   ngsld_prune_params p{};
   std::vector<std::string> subset;
+  // from the call to the writer: the stats, the labels and the subset the call read, the site states it filled
+  ngsld_prune_stats st{};
+  std::vector<const char *> lab, sub;
+  std::vector<uint8_t> state;
 } prune;
 
 // ---- --decay_* (new): LD decay bins and fit on the device ----
@@ -135,6 +139,7 @@ struct DecayArgs {
   const char *n_ind = nullptr, *recomb_rate = nullptr;
   ngsld_decay_params p{};
   double n_ind_v = 0, recomb_rate_v = 1;
+  ngsld_decay_stats st{};  // from the call to the writer
 } decay;
 
 // ---- --blocks_* (new): LD block matrices of one region on the device ----
@@ -150,6 +155,7 @@ struct SiteArgs {
   const char *out = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
   bool is_signed = false;
   ngsld_site_ld_params p{};
+  ngsld_site_ld_stats st{};  // from the call to the writer
 } site;
 
 // ---- --cluster_* (new): LD clusters on the device ----
@@ -160,6 +166,7 @@ struct ClusterArgs {
   bool is_signed = false;
   uint64_t min_size_v = 2;
   ngsld_clusters_params p{};
+  ngsld_clusters_stats st{};  // from the call to the writer
 } cluster;
 
 // ---- --grid_* (new): the LD grid on the device ----
@@ -168,6 +175,8 @@ struct GridArgs {
   const char *out = nullptr, *bin_size = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *linked_min = nullptr;
   bool is_signed = false;
   ngsld_grid_params p{};
+  ngsld_grid_stats st{};  // from the call to the writer
+  std::vector<const char *> lab;
 } grid;
 
 // ---- --linked_* (new): the linked pairs on the device ----
@@ -183,6 +192,7 @@ struct ScanArgs {
   bool given = false;  // any --scan_* flag
   const char *out = nullptr, *half_window = nullptr, *ld = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr;
   ngsld_scan_params p{};
+  ngsld_scan_stats st{};  // from the call to the writer
 } scan;
 
 bool parse_double(const char *txt, double *out) {
@@ -474,11 +484,35 @@ FILE *open_or_die(const char *path) {
   return f;
 }
 
-void run_decay(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
+// Each of the six analyses that ngsld_analyze takes comes in three parts: stage_* sets up what its call reads and fills and
+// describes it as an entry of ngsld_analyze's list, run_* is the single call over the same state, write_* reads the result
+// through the getters and writes the files.  One output flag runs stage, run, write; several run every stage, one
+// ngsld_analyze, every write (main).
+ngsld_analysis analysis_entry(uint32_t kind, const void *params, void *stats, const char *const *labels = nullptr,
+                              uint8_t *site_state = nullptr) {
+  ngsld_analysis a{};
+  a.struct_size = sizeof(a);
+  a.kind = kind;
+  a.params = params;
+  a.stats = stats;
+  a.labels = labels;
+  a.site_state = site_state;
+  return a;
+}
+
+ngsld_analysis stage_decay(const Params &, const ngsld_pos *) {
+  decay.st = ngsld_decay_stats{};
+  decay.st.struct_size = sizeof(decay.st);
+  return analysis_entry(NGSLD_AN_DECAY, &decay.p, &decay.st);
+}
+
+void run_decay(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_decay(ctx, &decay.p, &decay.st) != NGSLD_OK) error("ngsld_decay", ngsld_last_error(ctx));
+}
+
+void write_decay(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
   DecayArgs &da = decay;
-  ngsld_decay_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_decay(ctx, &da.p, &st) != NGSLD_OK) error("ngsld_decay", ngsld_last_error(ctx));
+  const ngsld_decay_stats &st = da.st;
   const std::vector<int> fields = fields_of(da.p.fields);
   const size_t nf = fields.size();
   const uint64_t nb = st.bins;
@@ -565,11 +599,19 @@ void print_summaries(FILE *f, size_t nf, uint64_t n, uint64_t i, uint64_t rows, 
 
 // one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the
 // counted rows, then sum, mean, max and linked of every chosen statistic; NA for the mean and max of a site without rows
-void run_site(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+ngsld_analysis stage_site(const Params &, const ngsld_pos *) {
+  site.st = ngsld_site_ld_stats{};
+  site.st.struct_size = sizeof(site.st);
+  return analysis_entry(NGSLD_AN_SITE_LD, &site.p, &site.st);
+}
+
+void run_site(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_site_ld(ctx, &site.p, &site.st) != NGSLD_OK) error("ngsld_site_ld", ngsld_last_error(ctx));
+}
+
+void write_site(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
   SiteArgs &sa = site;
-  ngsld_site_ld_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_site_ld(ctx, &sa.p, &st) != NGSLD_OK) error("ngsld_site_ld", ngsld_last_error(ctx));
+  const ngsld_site_ld_stats &st = sa.st;
   const uint64_t n = pars.n_sites;
   const std::vector<int> fields = fields_of(sa.p.fields);
   const size_t nf = fields.size();
@@ -598,11 +640,19 @@ void run_site(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
 // one line per site of the input, in file order: its label up to the first TAB (without --pos: its 1-based index), the sites of
 // its window and of its two flanks, the rows inside the left flank, inside the right flank and across the site, then per chosen
 // statistic the three sums, zns and omega; NA where a ratio is not defined
-void run_scan(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+ngsld_analysis stage_scan(const Params &, const ngsld_pos *) {
+  scan.st = ngsld_scan_stats{};
+  scan.st.struct_size = sizeof(scan.st);
+  return analysis_entry(NGSLD_AN_SCAN, &scan.p, &scan.st);
+}
+
+void run_scan(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_scan(ctx, &scan.p, &scan.st) != NGSLD_OK) error("ngsld_scan", ngsld_last_error(ctx));
+}
+
+void write_scan(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
   ScanArgs &sa = scan;
-  ngsld_scan_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_scan(ctx, &sa.p, &st) != NGSLD_OK) error("ngsld_scan", ngsld_last_error(ctx));
+  const ngsld_scan_stats &st = sa.st;
   const uint64_t n = pars.n_sites;
   const std::vector<int> fields = fields_of(sa.p.fields);
   const size_t nf = fields.size();
@@ -648,13 +698,21 @@ void run_scan(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
 
 // one line per cell with rows, by chromosome (file order), bin1, bin2: the chromosome, the lower breaks b * B of the two
 // windows, the counted rows, then sum, mean, max and linked of every chosen statistic -- the long form geom_tile and image read
-void run_grid(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+ngsld_analysis stage_grid(const Params &pars, const ngsld_pos *pos) {
+  grid.lab.resize(pars.n_sites);
+  for (uint64_t s = 0; s < pars.n_sites; s++) grid.lab[s] = ngsld_host_label(pos, s);
+  grid.st = ngsld_grid_stats{};
+  grid.st.struct_size = sizeof(grid.st);
+  return analysis_entry(NGSLD_AN_GRID, &grid.p, &grid.st, grid.lab.data());
+}
+
+void run_grid(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_grid(ctx, &grid.p, grid.lab.data(), &grid.st) != NGSLD_OK) error("ngsld_grid", ngsld_last_error(ctx));
+}
+
+void write_grid(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
   GridArgs &ga = grid;
-  std::vector<const char *> lab(pars.n_sites);
-  for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
-  ngsld_grid_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_grid(ctx, &ga.p, lab.data(), &st) != NGSLD_OK) error("ngsld_grid", ngsld_last_error(ctx));
+  const ngsld_grid_stats &st = ga.st;
   const uint64_t n = st.cells, B = ga.p.bin_size;
   const std::vector<int> fields = fields_of(ga.p.fields);
   const size_t nf = fields.size();
@@ -688,11 +746,19 @@ void run_grid(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
 
 // --cluster_out: one line per site of the input, in file order, its cluster or NA; --cluster_table: one line per cluster of
 // at least --cluster_min_size sites, in id order
-void run_clusters(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+ngsld_analysis stage_clusters(const Params &, const ngsld_pos *) {
+  cluster.st = ngsld_clusters_stats{};
+  cluster.st.struct_size = sizeof(cluster.st);
+  return analysis_entry(NGSLD_AN_CLUSTERS, &cluster.p, &cluster.st);
+}
+
+void run_clusters(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_clusters(ctx, &cluster.p, &cluster.st) != NGSLD_OK) error("ngsld_clusters", ngsld_last_error(ctx));
+}
+
+void write_clusters(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
   ClusterArgs &ca = cluster;
-  ngsld_clusters_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_clusters(ctx, &ca.p, &st) != NGSLD_OK) error("ngsld_clusters", ngsld_last_error(ctx));
+  const ngsld_clusters_stats &st = ca.st;
   const uint64_t n = pars.n_sites;
   if (ca.out) {
     std::vector<uint32_t> id(n);
@@ -832,12 +898,13 @@ void write_labels(const char *path, const std::vector<const char *> &labels) {
   if (fclose(f) != 0) error(__FUNCTION__, "cannot write pruning output file!");
 }
 
-void run_prune(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+ngsld_analysis stage_prune(const Params &pars, const ngsld_pos *pos) {
   PruneArgs &pa = prune;
-  std::vector<const char *> lab(pars.n_sites, "(null)");
+  std::vector<const char *> &lab = pa.lab, &sub = pa.sub;
+  lab.assign(pars.n_sites, "(null)");
   if (pos)
     for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
-  std::vector<const char *> sub;
+  sub.clear();
   for (const std::string &x : pa.subset) sub.push_back(x.c_str());
   if (pa.subset_file) {
     pa.p.subset = sub.data();
@@ -845,10 +912,21 @@ void run_prune(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
   }
   static const char *const kEmpty[1] = {""};
   if (pa.subset_file && sub.empty()) pa.p.subset = kEmpty;  // (an empty subset: no site is a node)
-  std::vector<uint8_t> state(pars.n_sites);
-  ngsld_prune_stats st{};
-  st.struct_size = sizeof(st);
-  if (ngsld_prune(ctx, &pa.p, lab.data(), state.data(), &st) != NGSLD_OK) error("ngsld_prune", ngsld_last_error(ctx));
+  pa.state.assign(pars.n_sites, 0);
+  pa.st = ngsld_prune_stats{};
+  pa.st.struct_size = sizeof(pa.st);
+  return analysis_entry(NGSLD_AN_PRUNE, &pa.p, &pa.st, lab.data(), pa.state.data());
+}
+
+void run_prune(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
+  if (ngsld_prune(ctx, &prune.p, prune.lab.data(), prune.state.data(), &prune.st) != NGSLD_OK) error("ngsld_prune", ngsld_last_error(ctx));
+}
+
+void write_prune(ngsld_ctx *, const Params &pars, const ngsld_pos *) {
+  PruneArgs &pa = prune;
+  const ngsld_prune_stats &st = pa.st;
+  const std::vector<const char *> &lab = pa.lab;
+  const std::vector<uint8_t> &state = pa.state;
   std::vector<const char *> kept, excl;
   for (uint64_t s = 0; s < pars.n_sites; s++) {
     if (state[s] == 1) kept.push_back(lab[s]);
@@ -874,7 +952,11 @@ struct Family {
   bool *switch_on;             // ... and where it goes
   bool *given;                 // any flag of the family
   void (*check)(const Params &);  // once the reference's own arguments have been checked; only when given
+  // stage (what the call reads and fills, as an entry of ngsld_analyze's list), run (the single call), write (the files).  A
+  // family without a stage is a call of its own whatever else is asked for, and writes in run.
+  ngsld_analysis (*stage)(const Params &, const ngsld_pos *);
   void (*run)(ngsld_ctx *, const Params &, const ngsld_pos *);
+  void (*write)(ngsld_ctx *, const Params &, const ngsld_pos *);
   const char *timing;          // its line of the NGSLD_TIMING report
 };
 const Family kFamilies[] = {
@@ -882,37 +964,37 @@ const Family kFamilies[] = {
      {{"prune_out", &prune.out}, {"prune_excl", &prune.excl}, {"prune_subset", &prune.subset_file}, {"prune_field", &prune.field},
       {"prune_weight_type", &prune.type}, {"prune_precision", &prune.precision}, {"prune_max_kb_dist", &prune.max_kb_dist},
       {"prune_min_weight", &prune.min_weight}},
-     "prune_keep_heavy", &prune.keep_heavy, &prune.given, check_prune_args, run_prune, "pruning"},  // (a second pass of the pair kernels when the TSV was written too)
+     "prune_keep_heavy", &prune.keep_heavy, &prune.given, check_prune_args, stage_prune, run_prune, write_prune, "pruning"},  // (with one more of the six analyses: one run of the pair kernels for them all)
     {"decay_",
      {{"decay_out", &decay.out}, {"decay_fit", &decay.fit}, {"decay_ld", &decay.ld}, {"decay_bin_size", &decay.bin_size},
       {"decay_max_kb_dist", &decay.max_kb_dist}, {"decay_min_maf", &decay.min_maf}, {"decay_n_ind", &decay.n_ind},
       {"decay_recomb_rate", &decay.recomb_rate}},
-     nullptr, nullptr, &decay.given, check_decay_args, run_decay, "LD decay"},  // (a pass of the pair kernels of its own)
+     nullptr, nullptr, &decay.given, check_decay_args, stage_decay, run_decay, write_decay, "LD decay"},
     {"blocks_",
      {{"blocks_out", &blocks.out}, {"blocks_chr", &blocks.chr}, {"blocks_start", &blocks.start}, {"blocks_end", &blocks.end},
       {"blocks_ld", &blocks.ld}},
-     nullptr, nullptr, &blocks.given, check_blocks_args, run_blocks, "LD blocks"},  // (a pass of the pair kernels over the region's rows)
+     nullptr, nullptr, &blocks.given, check_blocks_args, nullptr, run_blocks, nullptr, "LD blocks"},  // (a pass of the pair kernels over the region's rows)
     {"site_",
      {{"site_out", &site.out}, {"site_ld", &site.ld}, {"site_max_kb_dist", &site.max_kb_dist}, {"site_min_maf", &site.min_maf},
       {"site_linked_min", &site.linked_min}},
-     "site_signed", &site.is_signed, &site.given, check_site_args, run_site, "site LD"},  // (a pass of the pair kernels of its own)
+     "site_signed", &site.is_signed, &site.given, check_site_args, stage_site, run_site, write_site, "site LD"},
     {"cluster_",
      {{"cluster_out", &cluster.out}, {"cluster_table", &cluster.table}, {"cluster_field", &cluster.field},
       {"cluster_min_weight", &cluster.min_weight}, {"cluster_max_kb_dist", &cluster.max_kb_dist}, {"cluster_min_maf", &cluster.min_maf},
       {"cluster_min_size", &cluster.min_size}},
-     "cluster_signed", &cluster.is_signed, &cluster.given, check_cluster_args, run_clusters, "LD clusters"},  // (a pass of its own)
+     "cluster_signed", &cluster.is_signed, &cluster.given, check_cluster_args, stage_clusters, run_clusters, write_clusters, "LD clusters"},
     {"grid_",
      {{"grid_out", &grid.out}, {"grid_bin_size", &grid.bin_size}, {"grid_ld", &grid.ld}, {"grid_max_kb_dist", &grid.max_kb_dist},
       {"grid_min_maf", &grid.min_maf}, {"grid_linked_min", &grid.linked_min}},
-     "grid_signed", &grid.is_signed, &grid.given, check_grid_args, run_grid, "LD grid"},  // (a pass of its own)
+     "grid_signed", &grid.is_signed, &grid.given, check_grid_args, stage_grid, run_grid, write_grid, "LD grid"},
     {"linked_",
      {{"linked_out", &linked.out}, {"linked_outH", &linked.outH}, {"linked_field", &linked.field},
       {"linked_min_weight", &linked.min_weight}, {"linked_max_kb_dist", &linked.max_kb_dist}, {"linked_min_maf", &linked.min_maf}},
-     "linked_signed", &linked.is_signed, &linked.given, check_linked_args, run_linked, "linked pairs"},  // (a pass of its own)
+     "linked_signed", &linked.is_signed, &linked.given, check_linked_args, nullptr, run_linked, nullptr, "linked pairs"},  // (a pass of the pair kernels of its own: the 40 B records, a sink)
     {"scan_",
      {{"scan_out", &scan.out}, {"scan_half_window", &scan.half_window}, {"scan_ld", &scan.ld}, {"scan_max_kb_dist", &scan.max_kb_dist},
       {"scan_min_maf", &scan.min_maf}},
-     nullptr, nullptr, &scan.given, check_scan_args, run_scan, "LD scan"},  // (a pass of its own)
+     nullptr, nullptr, &scan.given, check_scan_args, stage_scan, run_scan, write_scan, "LD scan"},
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1662,9 +1744,24 @@ int main(int argc, char **argv) {
   timing_report.mark("pair kernels + text + write");
   if (rc == NGSLD_ERR_MAF_RANGE) error("haplo_freq", ngsld_last_error(ctx));
   if (rc != NGSLD_OK) error("ngsld_run", ngsld_last_error(ctx));
+  // two or more of the six analyses that read every planned pair share one run of the pair kernels (ngsld_analyze); the files
+  // are written in the families' order either way
+  std::vector<ngsld_analysis> bundle;
+  for (const Family &fam : kFamilies)
+    if (*fam.given && fam.stage != nullptr) bundle.push_back(fam.stage(pars, pos));
+  if (bundle.size() >= 2) {
+    ngsld_analyze_stats ast{};
+    ast.struct_size = sizeof(ast);
+    if (ngsld_analyze(ctx, bundle.data(), (uint32_t)bundle.size(), &ast) != NGSLD_OK) error("ngsld_analyze", ngsld_last_error(ctx));
+    if (pars.verbose >= 1)
+      fprintf(stderr, "==> analyses: %lu share one run of %lu pairs in %lu chunks\n", (unsigned long)bundle.size(),
+              (unsigned long)ast.pairs_run, (unsigned long)ast.chunks);
+    timing_report.mark("analyses (one run of the pair kernels)");
+  }
   for (const Family &fam : kFamilies)
     if (*fam.given) {
-      fam.run(ctx, pars, pos);
+      if (fam.stage == nullptr || bundle.size() < 2) fam.run(ctx, pars, pos);
+      if (fam.write != nullptr) fam.write(ctx, pars, pos);
       timing_report.mark(fam.timing);
     }
   if (write_tsv && pars.verbose >= 2) {  // (level 1 is the reference's default: its stderr stays what the reference prints.  A large share

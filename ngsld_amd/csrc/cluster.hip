@@ -145,155 +145,195 @@ __global__ __launch_bounds__(256) void flatten_kernel(uint32_t *parent, uint32_t
   if (r != (uint32_t)v) atomicMin(parent + v, r);
 }
 
+// ngsld_clusters in four parts (record_pass.h AnalysisPass)
+struct ClustersPass final : AnalysisPass {
+  const ngsld_clusters_params *p;
+  ngsld_clusters_stats *stats;
+  const std::chrono::steady_clock::time_point t_all = std::chrono::steady_clock::now();
+  ngsld_clusters_stats S;
+  SiteFilter F;
+  std::vector<uint32_t> parent;
+  std::vector<uint8_t> node;
+  std::vector<unsigned long long> acc;
+  bool track_max = false;
+  DevBuf<uint32_t> d_parent;
+  DevBuf<uint8_t> d_node;
+  DevBuf<unsigned long long> d_acc, d_meta;
+  ClusterArgs A{};
+
+  ClustersPass(const ngsld_clusters_params *params, ngsld_clusters_stats *out) : p(params), stats(out) {}
+
+  int validate(ngsld_ctx *c) override {
+    if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+    if (const int rc = check_struct_sizes(c, p, "ngsld_clusters_params", stats, "ngsld_clusters_stats")) return rc;
+    if (p->field < 4 || p->field > 7) return fail(c, NGSLD_ERR_INVALID, "clusters field must be a TSV column 4..7");
+    if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "clusters max_kb_dist must be >= 0");
+    if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "clusters min_maf is NaN");
+    if (std::isnan(p->min_weight)) return fail(c, NGSLD_ERR_INVALID, "clusters min_weight is NaN");
+    return NGSLD_OK;
+  }
+
+  void clear(ngsld_ctx *c) override { c->clear_clusters(); }
+
+  int prepare(ngsld_ctx *c, uint64_t) override {
+    const uint64_t n = c->n_sites;
+    if (const int rc = begin_pass(c, S)) return rc;
+    clear(c);
+    hipStream_t st = c->stream;
+
+    // ---- sites: the dist prefix sums (the limit and the spans come from them), the maf filter on the printed maf ----
+    F.prepare(c, &p->min_maf);
+    if (!F.exact_gaps) return fail(c, NGSLD_ERR_UNSUPPORTED, "clusters need integer position gaps");
+    const uint64_t n_pairs = c->h_row_off[n];
+    S.pairs = n_pairs;
+
+    parent.resize(n);
+    node.assign(n, 0);
+    acc.assign(2 * n, 0);
+    for (uint64_t s = 0; s < n; ++s) parent[s] = (uint32_t)s;
+    // every partial sum of a cluster is exact while max |q| * its edges < 2^63: certain below 2^25 edges (|q| < 2^38)
+    track_max = track_sums(n_pairs >= (1ull << 25));
+    if (n_pairs > 0) {
+      if (const int rc = F.upload(c)) return rc;
+      HIP_TRY(c, d_parent.resize(n));
+      HIP_TRY(c, d_node.resize(n));
+      HIP_TRY(c, d_acc.resize(2 * n));
+      HIP_TRY(c, d_meta.resize(2));
+      HIP_TRY(c, hipMemsetAsync(d_node.p, 0, n, st));
+      HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, 2 * n * sizeof(unsigned long long), st));
+      HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
+      hipLaunchKernelGGL(init_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_parent.p, (uint32_t)n);
+      HIP_TRY(c, hipGetLastError());
+      A.cum = F.d_cum.p;
+      A.infc = F.d_infc.p;
+      A.maf_ok = F.d_maf_ok.p;
+      A.limit = p->max_kb_dist * 1000.0;
+      A.min_weight = p->min_weight;
+      A.field = p->field - 4;
+      A.abs_value = p->abs_value != 0 ? 1 : 0;
+      A.track_max = track_max ? 1 : 0;
+      A.n_sites = (uint32_t)n;
+      A.parent = d_parent.p;
+      A.node = d_node.p;
+      A.acc = d_acc.p;
+      A.meta = d_meta.p;
+      const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
+      client.kernel_ms = &S.union_ms;
+      client.launch = [this, st, max_blocks](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+        A.out_base = ch.out_base;
+        A.items = items;
+        A.n_items = n_items;
+        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+        hipLaunchKernelGGL(union_kernel, dim3(blocks), dim3(256), 0, st, A);
+        ++S.union_launches;
+      };
+      client.after = [this, c, st](const RecordChunk &) -> int {
+        unsigned long long bad = 0;
+        HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        return bad != 0 ? fail_value_range(c, "clusters", bad) : NGSLD_OK;
+      };
+    }
+    return NGSLD_OK;
+  }
+
+  void bind(ngsld_rec_std *records) override { A.rec = records; }
+
+  int finish(ngsld_ctx *c, const RecordPass::Shared &shared) override {
+    const uint64_t n = c->n_sites;
+    hipStream_t st = c->stream;
+    unsigned long long meta[2] = {0, 0};
+    if (client.launch) {
+      S.pairs_ms = shared.pairs_ms;
+      S.chunks = shared.chunks;
+      const auto t_fin = std::chrono::steady_clock::now();
+      hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_parent.p, (uint32_t)n);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipMemcpyAsync(parent.data(), d_parent.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(node.data(), d_node.p, n, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(acc.data(), d_acc.p, 2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      S.finish_ms = ms_since(t_fin);
+    }
+
+    // ---- the clusters: a root is the smallest site of its component, so the roots come in id order ----
+    const auto t_host = std::chrono::steady_clock::now();
+    ngsld_ctx::Clusters &K = c->clusters;
+    K.id.assign(n, 0);
+    for (uint64_t s = 0; s < n; ++s) {
+      if (!node[s]) continue;
+      ++S.nodes;
+      const uint32_t root = parent[s];
+      if (root == s) {
+        K.size.push_back(0);
+        K.first.push_back((uint32_t)s);
+        K.last.push_back((uint32_t)s);
+        K.edges.push_back(0);
+        K.sum.push_back(0);
+        K.id[s] = (uint32_t)K.size.size();
+      } else {
+        if (root > s || K.id[root] == 0) return fail(c, NGSLD_ERR_DEVICE, "clusters: the forest is not flat");  // (cannot happen)
+        K.id[s] = K.id[root];
+      }
+      const size_t k = K.id[s] - 1;
+      ++K.size[k];
+      K.last[k] = (uint32_t)s;
+      K.edges[k] += acc[s];
+      K.sum[k] = (int64_t)((uint64_t)K.sum[k] + acc[n + s]);  // (two's complement, as on the device: checked below before it is read)
+    }
+    const size_t nk = K.size.size();
+    K.span.resize(nk);
+    K.mean.resize(nk);
+    K.density.resize(nk);
+    {  // the cluster of the most edges bounds every other's sums: the refusal names it
+      const uint64_t most = nk ? *std::max_element(K.edges.begin(), K.edges.end()) : 0;
+      if (track_max && track_sums(most >= (1ull << 25)) && sum_may_wrap(meta[1], most)) {
+        c->clear_clusters();
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(most) + " edges with values too large to sum exactly");
+      }
+    }
+    for (size_t k = 0; k < nk; ++k) {
+      const uint64_t size = K.size[k], edges = K.edges[k];
+      S.edges += edges;
+      if (size >= 2) ++S.clusters_multi;
+      S.largest = std::max<uint64_t>(S.largest, size);
+      K.span[k] = (uint64_t)(F.cum[K.last[k]] - F.cum[K.first[k]]);
+      const int64_t sum = K.sum[k];
+      if (edges == 0) {
+        K.mean[k] = std::numeric_limits<double>::quiet_NaN();
+      } else {
+        const double m = div_nearest((unsigned __int128)(sum < 0 ? -(__int128)sum : (__int128)sum), (unsigned __int128)edges * 1000000u);
+        K.mean[k] = sum < 0 ? -m : m;
+      }
+      K.density[k] = size < 2 ? std::numeric_limits<double>::quiet_NaN()
+                              : div_nearest((unsigned __int128)edges, (unsigned __int128)size * (size - 1) / 2);
+    }
+    S.clusters = nk;
+    K.valid = true;
+    S.finish_ms += ms_since(t_host);
+    S.total_ms = ms_since(t_all);
+    copy_stats(stats, S);
+    return NGSLD_OK;
+  }
+};
+
 }  // namespace
+
+namespace ngsld {
+namespace eng {
+std::unique_ptr<AnalysisPass> make_clusters_pass(const ngsld_clusters_params *p, ngsld_clusters_stats *stats) {
+  return std::unique_ptr<AnalysisPass>(new ClustersPass(p, stats));
+}
+}  // namespace eng
+}  // namespace ngsld
 
 extern "C" {
 
 int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_stats *stats) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  const auto t_all = std::chrono::steady_clock::now();
-  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (const int rc = check_struct_sizes(c, p, "ngsld_clusters_params", stats, "ngsld_clusters_stats")) return rc;
-  if (p->field < 4 || p->field > 7) return fail(c, NGSLD_ERR_INVALID, "clusters field must be a TSV column 4..7");
-  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "clusters max_kb_dist must be >= 0");
-  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "clusters min_maf is NaN");
-  if (std::isnan(p->min_weight)) return fail(c, NGSLD_ERR_INVALID, "clusters min_weight is NaN");
-  const uint64_t n = c->n_sites;
-  ngsld_clusters_stats S;
-  if (const int rc = begin_pass(c, S)) return rc;
-  c->clear_clusters();
-  hipStream_t st = c->stream;
-
-  // ---- sites: the dist prefix sums (the limit and the spans come from them), the maf filter on the printed maf ----
-  SiteFilter F;
-  F.prepare(c, &p->min_maf);
-  if (!F.exact_gaps) return fail(c, NGSLD_ERR_UNSUPPORTED, "clusters need integer position gaps");
-  const uint64_t chunk = record_chunk(test_knob("CLUSTER_CHUNK_PAIRS"));
-  const uint64_t n_pairs = c->h_row_off[n];
-  S.pairs = n_pairs;
-
-  std::vector<uint32_t> parent(n);
-  std::vector<uint8_t> node(n, 0);
-  std::vector<unsigned long long> acc(2 * n, 0);
-  for (uint64_t s = 0; s < n; ++s) parent[s] = (uint32_t)s;
-  unsigned long long meta[2] = {0, 0};
-  // every partial sum of a cluster is exact while max |q| * its edges < 2^63: certain below 2^25 edges (|q| < 2^38)
-  const bool track_max = track_sums(n_pairs >= (1ull << 25));
-  if (n_pairs > 0) {
-    DevBuf<uint32_t> d_parent;
-    DevBuf<uint8_t> d_node;
-    DevBuf<unsigned long long> d_acc, d_meta;
-    if (const int rc = F.upload(c)) return rc;
-    HIP_TRY(c, d_parent.resize(n));
-    HIP_TRY(c, d_node.resize(n));
-    HIP_TRY(c, d_acc.resize(2 * n));
-    HIP_TRY(c, d_meta.resize(2));
-    HIP_TRY(c, hipMemsetAsync(d_node.p, 0, n, st));
-    HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, 2 * n * sizeof(unsigned long long), st));
-    HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(init_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_parent.p, (uint32_t)n);
-    HIP_TRY(c, hipGetLastError());
-    RecordPass R;
-    if (const int rc = R.open(c, chunk)) return rc;
-    ClusterArgs A{};
-    A.rec = R.records();
-    A.cum = F.d_cum.p;
-    A.infc = F.d_infc.p;
-    A.maf_ok = F.d_maf_ok.p;
-    A.limit = p->max_kb_dist * 1000.0;
-    A.min_weight = p->min_weight;
-    A.field = p->field - 4;
-    A.abs_value = p->abs_value != 0 ? 1 : 0;
-    A.track_max = track_max ? 1 : 0;
-    A.n_sites = (uint32_t)n;
-    A.parent = d_parent.p;
-    A.node = d_node.p;
-    A.acc = d_acc.p;
-    A.meta = d_meta.p;
-    const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
-    const int rc = R.run(&S.pairs_ms, &S.union_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
-      A.out_base = ch.out_base;
-      A.items = items;
-      A.n_items = n_items;
-      const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-      hipLaunchKernelGGL(union_kernel, dim3(blocks), dim3(256), 0, st, A);
-      ++S.union_launches;
-    }, [&](const RecordChunk &) -> int {
-      unsigned long long bad = 0;
-      HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      return bad != 0 ? fail_value_range(c, "clusters", bad) : NGSLD_OK;
-    });
-    if (rc != NGSLD_OK) return rc;
-    const auto t_fin = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_parent.p, (uint32_t)n);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(parent.data(), d_parent.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(node.data(), d_node.p, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(acc.data(), d_acc.p, 2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    S.finish_ms = ms_since(t_fin);
-  }
-
-  // ---- the clusters: a root is the smallest site of its component, so the roots come in id order ----
-  const auto t_host = std::chrono::steady_clock::now();
-  ngsld_ctx::Clusters &K = c->clusters;
-  K.id.assign(n, 0);
-  for (uint64_t s = 0; s < n; ++s) {
-    if (!node[s]) continue;
-    ++S.nodes;
-    const uint32_t root = parent[s];
-    if (root == s) {
-      K.size.push_back(0);
-      K.first.push_back((uint32_t)s);
-      K.last.push_back((uint32_t)s);
-      K.edges.push_back(0);
-      K.sum.push_back(0);
-      K.id[s] = (uint32_t)K.size.size();
-    } else {
-      if (root > s || K.id[root] == 0) return fail(c, NGSLD_ERR_DEVICE, "clusters: the forest is not flat");  // (cannot happen)
-      K.id[s] = K.id[root];
-    }
-    const size_t k = K.id[s] - 1;
-    ++K.size[k];
-    K.last[k] = (uint32_t)s;
-    K.edges[k] += acc[s];
-    K.sum[k] = (int64_t)((uint64_t)K.sum[k] + acc[n + s]);  // (two's complement, as on the device: checked below before it is read)
-  }
-  const size_t nk = K.size.size();
-  K.span.resize(nk);
-  K.mean.resize(nk);
-  K.density.resize(nk);
-  {  // the cluster of the most edges bounds every other's sums: the refusal names it
-    const uint64_t most = nk ? *std::max_element(K.edges.begin(), K.edges.end()) : 0;
-    if (track_max && track_sums(most >= (1ull << 25)) && sum_may_wrap(meta[1], most)) {
-      c->clear_clusters();
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(most) + " edges with values too large to sum exactly");
-    }
-  }
-  for (size_t k = 0; k < nk; ++k) {
-    const uint64_t size = K.size[k], edges = K.edges[k];
-    S.edges += edges;
-    if (size >= 2) ++S.clusters_multi;
-    S.largest = std::max<uint64_t>(S.largest, size);
-    K.span[k] = (uint64_t)(F.cum[K.last[k]] - F.cum[K.first[k]]);
-    const int64_t sum = K.sum[k];
-    if (edges == 0) {
-      K.mean[k] = std::numeric_limits<double>::quiet_NaN();
-    } else {
-      const double m = div_nearest((unsigned __int128)(sum < 0 ? -(__int128)sum : (__int128)sum), (unsigned __int128)edges * 1000000u);
-      K.mean[k] = sum < 0 ? -m : m;
-    }
-    K.density[k] = size < 2 ? std::numeric_limits<double>::quiet_NaN()
-                            : div_nearest((unsigned __int128)edges, (unsigned __int128)size * (size - 1) / 2);
-  }
-  S.clusters = nk;
-  K.valid = true;
-  S.finish_ms += ms_since(t_host);
-  S.total_ms = ms_since(t_all);
-  copy_stats(stats, S);
-  return NGSLD_OK;
+  ClustersPass pass(p, stats);
+  return run_single(c, pass, record_chunk(test_knob("CLUSTER_CHUNK_PAIRS")));
 } NGSLD_CATCH(c)
 
 int ngsld_clusters_sites(ngsld_ctx *c, uint32_t *cluster) {

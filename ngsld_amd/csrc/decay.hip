@@ -155,88 +155,100 @@ double break_value(uint64_t k, double B) {
   return std::strtod(buf, nullptr);
 }
 
-}  // namespace
-
-extern "C" {
-
-int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *stats) try {
-  if (c == nullptr) return NGSLD_ERR_INVALID;
-  const auto t_all = std::chrono::steady_clock::now();
-  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (const int rc = check_struct_sizes(c, p, "ngsld_decay_params", stats, "ngsld_decay_stats")) return rc;
-  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "decay fields must be a non-empty mask of 1, 2, 4, 8");
-  if (!(p->bin_size > 1.0) || !std::isfinite(p->bin_size)) return fail(c, NGSLD_ERR_INVALID, "decay bin_size must be a finite number > 1");
-  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "decay max_kb_dist must be >= 0");
-  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "decay min_maf is NaN");
-  const uint64_t n = c->n_sites;
+// ngsld_decay in four parts (record_pass.h AnalysisPass)
+struct DecayPass final : AnalysisPass {
+  const ngsld_decay_params *p;
+  ngsld_decay_stats *stats;
+  const std::chrono::steady_clock::time_point t_all = std::chrono::steady_clock::now();
   ngsld_decay_stats S;
-  if (const int rc = begin_pass(c, S)) return rc;
-  c->decay_fields = 0;
-  c->decay_dist.clear();
-  c->decay_mean.clear();
-  c->decay_count.clear();
-  hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0};
-  const int ns = field_list(p->fields, field);
-  const double B = p->bin_size;
-
-  // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
-  const double limit = p->max_kb_dist * 1000.0;
   SiteFilter F;
-  F.prepare(c, &p->min_maf);
-  if (const int rc = F.check_limit(c, "decay", limit)) return rc;
-  const std::vector<double> &cum = F.cum;
-  const std::vector<uint32_t> &infc = F.infc;
+  int field[4] = {0, 0, 0, 0};
+  int ns = 0;
+  uint64_t n_slots = 0, W = 0, chunk = 0;
+  bool use_lds = false;
+  std::vector<unsigned __int128> sum;
+  std::vector<uint64_t> count;
+  DevBuf<unsigned long long> d_acc, d_meta;
+  std::vector<unsigned long long> h_acc;
+  BinArgs A{};
 
-  // ---- bins sized from the plan: the largest finite planned dist, capped by the limit ----
-  uint64_t n_slots = 0;
-  {
-    std::vector<uint64_t> chr_last(n ? (size_t)infc[n - 1] + 1 : 0, 0);
-    std::vector<double> chr_lo(chr_last.size(), INFINITY), chr_hi(chr_last.size(), -INFINITY);
-    for (uint64_t s = 0; s < n; ++s) {
-      chr_last[infc[s]] = s;
-      chr_lo[infc[s]] = std::min(chr_lo[infc[s]], cum[s]);
-      chr_hi[infc[s]] = std::max(chr_hi[infc[s]], cum[s]);
-    }
-    double dmax = 0.0;
-    for (uint64_t s1 = 0; s1 < n; ++s1) {
-      if (c->h_row_off[s1 + 1] == c->h_row_off[s1]) continue;
-      const uint64_t s2 = std::min<uint64_t>(c->h_row_end[s1] - 1, chr_last[infc[s1]]);
-      if (s2 <= s1) continue;
-      // gaps >= 0 (every position file): dist rises along the row; any other gaps: the chromosome's span bounds it
-      const double d = F.exact_gaps ? cum[s2] - cum[s1] : chr_hi[infc[s1]] - chr_lo[infc[s1]];
-      dmax = std::max(dmax, printed_dist(d));
-    }
-    if (dmax >= limit) dmax = limit;  // (dist < limit: the limit's own bin is the last one that can fill)
-    const long long kmax = bin_of(dmax, B);
-    if (kmax >= 0) {
-      if ((uint64_t)kmax >= kMaxSlots)
-        return fail(c, NGSLD_ERR_UNSUPPORTED, "more than 2^22 decay bins (raise bin_size or set max_kb_dist)");
-      n_slots = (uint64_t)kmax + 1;
-    }
+  DecayPass(const ngsld_decay_params *params, ngsld_decay_stats *out) : p(params), stats(out) {}
+
+  int validate(ngsld_ctx *c) override {
+    if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+    if (const int rc = check_struct_sizes(c, p, "ngsld_decay_params", stats, "ngsld_decay_stats")) return rc;
+    if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "decay fields must be a non-empty mask of 1, 2, 4, 8");
+    if (!(p->bin_size > 1.0) || !std::isfinite(p->bin_size)) return fail(c, NGSLD_ERR_INVALID, "decay bin_size must be a finite number > 1");
+    if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "decay max_kb_dist must be >= 0");
+    if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "decay min_maf is NaN");
+    return NGSLD_OK;
   }
-  S.bin_slots = n_slots;
-  const uint64_t W = (uint64_t)(1 + ns) * n_slots;
-  uint64_t lds_budget = kLdsBudget;
-  if (const char *e = test_knob("DECAY_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), 64u << 10);
-  const bool use_lds = W > 0 && W * 8 <= lds_budget;
-  S.lds = use_lds ? 1 : 0;
-  const uint64_t chunk = record_chunk(test_knob("DECAY_CHUNK_PAIRS"));
 
-  const uint64_t n_pairs = c->h_row_off[n];
-  S.pairs = n_pairs;
-  std::vector<unsigned __int128> sum(ns * n_slots, 0);
-  std::vector<uint64_t> count(n_slots, 0);
-  if (n_slots > 0 && n_pairs > 0) {
-    DevBuf<unsigned long long> d_acc, d_meta;
+  void clear(ngsld_ctx *c) override {
+    c->decay_fields = 0;
+    c->decay_dist.clear();
+    c->decay_mean.clear();
+    c->decay_count.clear();
+  }
+
+  int prepare(ngsld_ctx *c, uint64_t chunk_pairs) override {
+    const uint64_t n = c->n_sites;
+    if (const int rc = begin_pass(c, S)) return rc;
+    clear(c);
+    hipStream_t st = c->stream;
+    ns = field_list(p->fields, field);
+    const double B = p->bin_size;
+    chunk = chunk_pairs;
+
+    // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
+    const double limit = p->max_kb_dist * 1000.0;
+    F.prepare(c, &p->min_maf);
+    if (const int rc = F.check_limit(c, "decay", limit)) return rc;
+    const std::vector<double> &cum = F.cum;
+    const std::vector<uint32_t> &infc = F.infc;
+
+    // ---- bins sized from the plan: the largest finite planned dist, capped by the limit ----
+    {
+      std::vector<uint64_t> chr_last(n ? (size_t)infc[n - 1] + 1 : 0, 0);
+      std::vector<double> chr_lo(chr_last.size(), INFINITY), chr_hi(chr_last.size(), -INFINITY);
+      for (uint64_t s = 0; s < n; ++s) {
+        chr_last[infc[s]] = s;
+        chr_lo[infc[s]] = std::min(chr_lo[infc[s]], cum[s]);
+        chr_hi[infc[s]] = std::max(chr_hi[infc[s]], cum[s]);
+      }
+      double dmax = 0.0;
+      for (uint64_t s1 = 0; s1 < n; ++s1) {
+        if (c->h_row_off[s1 + 1] == c->h_row_off[s1]) continue;
+        const uint64_t s2 = std::min<uint64_t>(c->h_row_end[s1] - 1, chr_last[infc[s1]]);
+        if (s2 <= s1) continue;
+        // gaps >= 0 (every position file): dist rises along the row; any other gaps: the chromosome's span bounds it
+        const double d = F.exact_gaps ? cum[s2] - cum[s1] : chr_hi[infc[s1]] - chr_lo[infc[s1]];
+        dmax = std::max(dmax, printed_dist(d));
+      }
+      if (dmax >= limit) dmax = limit;  // (dist < limit: the limit's own bin is the last one that can fill)
+      const long long kmax = bin_of(dmax, B);
+      if (kmax >= 0) {
+        if ((uint64_t)kmax >= kMaxSlots)
+          return fail(c, NGSLD_ERR_UNSUPPORTED, "more than 2^22 decay bins (raise bin_size or set max_kb_dist)");
+        n_slots = (uint64_t)kmax + 1;
+      }
+    }
+    S.bin_slots = n_slots;
+    W = (uint64_t)(1 + ns) * n_slots;
+    uint64_t lds_budget = kLdsBudget;
+    if (const char *e = test_knob("DECAY_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), 64u << 10);
+    use_lds = W > 0 && W * 8 <= lds_budget;
+    S.lds = use_lds ? 1 : 0;
+
+    const uint64_t n_pairs = c->h_row_off[n];
+    S.pairs = n_pairs;
+    sum.assign(ns * n_slots, 0);
+    count.assign(n_slots, 0);
+    if (n_slots == 0 || n_pairs == 0) return NGSLD_OK;
     if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_acc.resize(W));
     HIP_TRY(c, d_meta.resize(3));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    RecordPass R;
-    if (const int rc = R.open(c, chunk)) return rc;
-    BinArgs A{};
-    A.rec = R.records();
     A.cum = F.d_cum.p;
     A.infc = F.d_infc.p;
     A.maf_ok = F.d_maf_ok.p;
@@ -247,13 +259,15 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
     for (int v = 0; v < 4; ++v) A.field[v] = field[v];
     A.acc = d_acc.p;
     A.meta = d_meta.p;
-    std::vector<unsigned long long> h_acc(W);
+    h_acc.resize(W);
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    const int rc = R.run(&S.pairs_ms, &S.bin_ms, &S.chunks, [&](const RecordChunk &ch) -> int {
+    client.kernel_ms = &S.bin_ms;
+    client.before = [this, c, st](const RecordChunk &ch) -> int {
       A.track_max = track_sums(ch.pairs > chunk) ? 1 : 0;
       HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
       return NGSLD_OK;
-    }, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+    };
+    client.launch = [this, st, max_blocks](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
       A.out_base = ch.out_base;
       A.items = items;
       A.n_items = n_items;
@@ -262,7 +276,8 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
         hipLaunchKernelGGL(bin_kernel<true>, dim3(blocks), dim3(256), (size_t)W * 8, st, A);
       else
         hipLaunchKernelGGL(bin_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-    }, [&](const RecordChunk &ch) -> int {
+    };
+    client.after = [this, c, st](const RecordChunk &ch) -> int {
       unsigned long long meta[3] = {0, 0, 0};
       HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
@@ -277,28 +292,55 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
         for (int v = 0; v < ns; ++v) sum[v * n_slots + k] += (unsigned __int128)(__int128)(int64_t)h_acc[(1 + v) * n_slots + k];
       }
       return NGSLD_OK;
-    });
-    if (rc != NGSLD_OK) return rc;
+    };
+    return NGSLD_OK;
   }
 
-  // ---- the means: exact integer sums, one rounding ----
-  for (uint64_t k = 0; k < n_slots; ++k) {
-    if (count[k] == 0) continue;
-    c->decay_dist.push_back(break_value(k, B));
-    c->decay_count.push_back(count[k]);
-    S.pairs_counted += count[k];
-    for (int v = 0; v < ns; ++v) {
-      const __int128 s = (__int128)sum[v * n_slots + k];
-      const unsigned __int128 a = (unsigned __int128)(s < 0 ? -s : s), b = (unsigned __int128)count[k] * 1000000u;
-      const double m = div_nearest(a, b);
-      c->decay_mean.push_back(s < 0 ? -m : m);
+  void bind(ngsld_rec_std *records) override { A.rec = records; }
+
+  int finish(ngsld_ctx *c, const RecordPass::Shared &shared) override {
+    if (client.launch) {
+      S.pairs_ms = shared.pairs_ms;
+      S.chunks = shared.chunks;
     }
+    // ---- the means: exact integer sums, one rounding ----
+    const double B = p->bin_size;
+    for (uint64_t k = 0; k < n_slots; ++k) {
+      if (count[k] == 0) continue;
+      c->decay_dist.push_back(break_value(k, B));
+      c->decay_count.push_back(count[k]);
+      S.pairs_counted += count[k];
+      for (int v = 0; v < ns; ++v) {
+        const __int128 s = (__int128)sum[v * n_slots + k];
+        const unsigned __int128 a = (unsigned __int128)(s < 0 ? -s : s), b = (unsigned __int128)count[k] * 1000000u;
+        const double m = div_nearest(a, b);
+        c->decay_mean.push_back(s < 0 ? -m : m);
+      }
+    }
+    c->decay_fields = p->fields;
+    S.bins = c->decay_count.size();
+    S.total_ms = ms_since(t_all);
+    copy_stats(stats, S);
+    return NGSLD_OK;
   }
-  c->decay_fields = p->fields;
-  S.bins = c->decay_count.size();
-  S.total_ms = ms_since(t_all);
-  copy_stats(stats, S);
-  return NGSLD_OK;
+};
+
+}  // namespace
+
+namespace ngsld {
+namespace eng {
+std::unique_ptr<AnalysisPass> make_decay_pass(const ngsld_decay_params *p, ngsld_decay_stats *stats) {
+  return std::unique_ptr<AnalysisPass>(new DecayPass(p, stats));
+}
+}  // namespace eng
+}  // namespace ngsld
+
+extern "C" {
+
+int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *stats) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  DecayPass pass(p, stats);
+  return run_single(c, pass, record_chunk(test_knob("DECAY_CHUNK_PAIRS")));
 } NGSLD_CATCH(c)
 
 int ngsld_decay_bins(ngsld_ctx *c, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins) {

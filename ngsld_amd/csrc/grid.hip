@@ -209,248 +209,287 @@ __global__ __launch_bounds__(256) void grid_kernel(GridArgs A) {
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labels, ngsld_grid_stats *stats) try {
-  if (c == nullptr) return NGSLD_ERR_INVALID;
-  const auto t_all = std::chrono::steady_clock::now();
-  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (const int rc = check_struct_sizes(c, p, "ngsld_grid_params", stats, "ngsld_grid_stats")) return rc;
-  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "grid fields must be a non-empty mask of 1, 2, 4, 8");
-  if (p->bin_size < 1 || p->bin_size >= (1ull << 31)) return fail(c, NGSLD_ERR_INVALID, "grid bin_size must be an integer in [1, 2^31)");
-  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "grid max_kb_dist must be >= 0");
-  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "grid min_maf is NaN");
-  if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "grid linked_min is NaN");
-  if (labels == nullptr) return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: the labels are NULL");
-  const uint64_t n = c->n_sites;
+// ngsld_grid in four parts (record_pass.h AnalysisPass)
+struct GridPass final : AnalysisPass {
+  const ngsld_grid_params *p;
+  const char *const *labels;
+  ngsld_grid_stats *stats;
+  const std::chrono::steady_clock::time_point t_all = std::chrono::steady_clock::now();
   ngsld_grid_stats S;
-  if (const int rc = begin_pass(c, S)) return rc;
-  c->clear_grid();
-  hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0};
-  const int ns = field_list(p->fields, field);
-  const uint32_t words = 1u + 3u * (uint32_t)ns;
-  const uint64_t B = p->bin_size;
-
-  // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
-  const double limit = p->max_kb_dist * 1000.0;
   SiteFilter F;
-  F.prepare(c, &p->min_maf);
-  if (const int rc = F.check_limit(c, "grid", limit)) return rc;
-
-  // ---- bins: each label's CHR:pos; a chromosome is a run of sites between the +inf gaps of pos_dist ----
+  int field[4] = {0, 0, 0, 0};
+  int ns = 0;
+  uint32_t words = 0;
   struct Chr {
     std::string name;
     uint64_t first_site, last_site, first_bin, gbin0;  // gbin0: the consecutive number of its first bin
   };
   std::vector<Chr> chrs;
-  std::vector<uint32_t> gbin(n), chr_of(n);
-  uint64_t n_bins = 0;
-  {
-    std::unordered_set<std::string> seen;
-    std::string prev_key;
-    uint64_t prev_pos = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-      if (labels[s] == nullptr) return fail(c, NGSLD_ERR_INVALID, "a label is NULL");
-      const LabelPos L = label_pos(labels[s]);
-      const std::string &key = L.key, name = L.chr();
-      if (key == "(null)") return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: a label is \"(null)\"");
-      uint64_t pos = 0;
-      if (!L.position(&pos)) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of label \"" + key + "\" is not plain decimal digits");
-      const bool new_run = s == 0 || F.infc[s] != F.infc[s - 1];
-      if (new_run) {
-        if (s > 0 && name == chrs.back().name)
-          return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: site \"" + key + "\" is on the chromosome of the site before it, \"" + prev_key +
-                                                    "\", but their distance is not finite");
-        if (!seen.insert(name).second)
-          return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: chromosome \"" + name + "\" begins a second time at site \"" + key + "\"");
-        if (!chrs.empty()) n_bins = chrs.back().gbin0 + (prev_pos / B - chrs.back().first_bin) + 1;
-        chrs.push_back({name, s, s, pos / B, n_bins});
-      } else {
-        if (name != chrs.back().name)
-          return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: site \"" + key + "\" is on another chromosome than the site before it, \"" +
-                                                    prev_key + "\", but their distance is finite");
-        if (pos < prev_pos)
-          return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of site \"" + key + "\" is below that of the site before it, \"" +
-                                                    prev_key + "\"");
-      }
-      Chr &ch = chrs.back();
-      ch.last_site = s;
-      const uint64_t g = ch.gbin0 + (pos / B - ch.first_bin);
-      if (g >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: more than 2^32 - 1 bins up to site \"" + key + "\": a larger bin_size is needed");
-      gbin[s] = (uint32_t)g;
-      chr_of[s] = (uint32_t)(chrs.size() - 1);
-      prev_key = key;
-      prev_pos = pos;
-    }
-    if (!chrs.empty()) n_bins = chrs.back().gbin0 + (prev_pos / B - chrs.back().first_bin) + 1;
+  uint64_t n_bins = 0, band = 0, cells = 0, cell_rows = 0, tile_bins = 1;
+  bool use_lds = false;
+  size_t W = 0, lds_bytes = 0;
+  std::vector<unsigned long long> h_acc;
+  DevBuf<uint32_t> d_gbin;
+  DevBuf<unsigned long long> d_acc, d_meta;
+  GridArgs A{};
+
+  GridPass(const ngsld_grid_params *params, const char *const *site_labels, ngsld_grid_stats *out)
+      : p(params), labels(site_labels), stats(out) {}
+
+  int validate(ngsld_ctx *c) override {
+    if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+    if (const int rc = check_struct_sizes(c, p, "ngsld_grid_params", stats, "ngsld_grid_stats")) return rc;
+    if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "grid fields must be a non-empty mask of 1, 2, 4, 8");
+    if (p->bin_size < 1 || p->bin_size >= (1ull << 31)) return fail(c, NGSLD_ERR_INVALID, "grid bin_size must be an integer in [1, 2^31)");
+    if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "grid max_kb_dist must be >= 0");
+    if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "grid min_maf is NaN");
+    if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "grid linked_min is NaN");
+    if (labels == nullptr) return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: the labels are NULL");
+    return NGSLD_OK;
   }
 
-  // ---- from the plan: the band (how many bins a row's candidates reach), the row bins of a tile, the rows a cell can hold ----
-  uint64_t band = 0;
-  for (uint64_t s = 0; s < n; ++s) {
-    if (c->h_row_off[s + 1] == c->h_row_off[s] || c->h_row_end[s] <= s + 1) continue;
-    const uint64_t far = std::min<uint64_t>(c->h_row_end[s] - 1, chrs[chr_of[s]].last_site);  // (never across a chromosome)
-    band = std::max<uint64_t>(band, (uint64_t)gbin[far] - gbin[s] + 1);
-  }
-  const uint64_t n_pairs = c->h_row_off[n];
-  S.pairs = n_pairs;
-  S.bins = n_bins;
-  S.band = band;
-  const uint64_t cells = n_bins * band;  // (both below 2^32)
-  if ((unsigned __int128)cells * words * 8 > kMaxAccBytes)
-    return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: " + std::to_string(n_bins) + " bins x a band of " + std::to_string(band) + " = " +
-                                              std::to_string(cells) + " cells, whose accumulators pass 2 GiB: a larger bin_size is needed");
-  // the most rows a cell can hold: the two largest bin populations p1 >= p2 give p1 * p2 between two bins and p1 * (p1 - 1) / 2
-  // inside one; or every pair, if that is fewer
-  uint64_t cell_rows = 0;
-  {
-    uint64_t top1 = 0, top2 = 0, run = 0;
+  void clear(ngsld_ctx *c) override { c->clear_grid(); }
+
+  int prepare(ngsld_ctx *c, uint64_t) override {
+    const uint64_t n = c->n_sites;
+    if (const int rc = begin_pass(c, S)) return rc;
+    clear(c);
+    hipStream_t st = c->stream;
+    ns = field_list(p->fields, field);
+    words = 1u + 3u * (uint32_t)ns;
+    const uint64_t B = p->bin_size;
+
+    // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
+    const double limit = p->max_kb_dist * 1000.0;
+    F.prepare(c, &p->min_maf);
+    if (const int rc = F.check_limit(c, "grid", limit)) return rc;
+
+    // ---- bins: each label's CHR:pos; a chromosome is a run of sites between the +inf gaps of pos_dist ----
+    std::vector<uint32_t> gbin(n), chr_of(n);
+    {
+      std::unordered_set<std::string> seen;
+      std::string prev_key;
+      uint64_t prev_pos = 0;
+      for (uint64_t s = 0; s < n; ++s) {
+        if (labels[s] == nullptr) return fail(c, NGSLD_ERR_INVALID, "a label is NULL");
+        const LabelPos L = label_pos(labels[s]);
+        const std::string &key = L.key, name = L.chr();
+        if (key == "(null)") return fail(c, NGSLD_ERR_INVALID, "the LD grid needs positions: a label is \"(null)\"");
+        uint64_t pos = 0;
+        if (!L.position(&pos)) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of label \"" + key + "\" is not plain decimal digits");
+        const bool new_run = s == 0 || F.infc[s] != F.infc[s - 1];
+        if (new_run) {
+          if (s > 0 && name == chrs.back().name)
+            return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: site \"" + key + "\" is on the chromosome of the site before it, \"" + prev_key +
+                                                      "\", but their distance is not finite");
+          if (!seen.insert(name).second)
+            return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: chromosome \"" + name + "\" begins a second time at site \"" + key + "\"");
+          if (!chrs.empty()) n_bins = chrs.back().gbin0 + (prev_pos / B - chrs.back().first_bin) + 1;
+          chrs.push_back({name, s, s, pos / B, n_bins});
+        } else {
+          if (name != chrs.back().name)
+            return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: site \"" + key + "\" is on another chromosome than the site before it, \"" +
+                                                      prev_key + "\", but their distance is finite");
+          if (pos < prev_pos)
+            return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: the position of site \"" + key + "\" is below that of the site before it, \"" +
+                                                      prev_key + "\"");
+        }
+        Chr &ch = chrs.back();
+        ch.last_site = s;
+        const uint64_t g = ch.gbin0 + (pos / B - ch.first_bin);
+        if (g >= 0xffffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: more than 2^32 - 1 bins up to site \"" + key + "\": a larger bin_size is needed");
+        gbin[s] = (uint32_t)g;
+        chr_of[s] = (uint32_t)(chrs.size() - 1);
+        prev_key = key;
+        prev_pos = pos;
+      }
+      if (!chrs.empty()) n_bins = chrs.back().gbin0 + (prev_pos / B - chrs.back().first_bin) + 1;
+    }
+
+    // ---- from the plan: the band (how many bins a row's candidates reach), the row bins of a tile, the rows a cell can hold ----
     for (uint64_t s = 0; s < n; ++s) {
-      run = (s > 0 && gbin[s] == gbin[s - 1]) ? run + 1 : 1;
-      if (s + 1 == n || gbin[s + 1] != gbin[s]) {
-        if (run > top1) {
-          top2 = top1;
-          top1 = run;
-        } else if (run > top2) {
-          top2 = run;
+      if (c->h_row_off[s + 1] == c->h_row_off[s] || c->h_row_end[s] <= s + 1) continue;
+      const uint64_t far = std::min<uint64_t>(c->h_row_end[s] - 1, chrs[chr_of[s]].last_site);  // (never across a chromosome)
+      band = std::max<uint64_t>(band, (uint64_t)gbin[far] - gbin[s] + 1);
+    }
+    const uint64_t n_pairs = c->h_row_off[n];
+    S.pairs = n_pairs;
+    S.bins = n_bins;
+    S.band = band;
+    cells = n_bins * band;  // (both below 2^32)
+    if ((unsigned __int128)cells * words * 8 > kMaxAccBytes)
+      return fail(c, NGSLD_ERR_UNSUPPORTED, "LD grid: " + std::to_string(n_bins) + " bins x a band of " + std::to_string(band) + " = " +
+                                                std::to_string(cells) + " cells, whose accumulators pass 2 GiB: a larger bin_size is needed");
+    // the most rows a cell can hold: the two largest bin populations p1 >= p2 give p1 * p2 between two bins and p1 * (p1 - 1) / 2
+    // inside one; or every pair, if that is fewer
+    {
+      uint64_t top1 = 0, top2 = 0, run = 0;
+      for (uint64_t s = 0; s < n; ++s) {
+        run = (s > 0 && gbin[s] == gbin[s - 1]) ? run + 1 : 1;
+        if (s + 1 == n || gbin[s + 1] != gbin[s]) {
+          if (run > top1) {
+            top2 = top1;
+            top1 = run;
+          } else if (run > top2) {
+            top2 = run;
+          }
         }
       }
+      const unsigned __int128 most = std::max((unsigned __int128)top1 * top2, (unsigned __int128)top1 * (top1 - (top1 > 0)) / 2);
+      cell_rows = most < n_pairs ? (uint64_t)most : n_pairs;
     }
-    const unsigned __int128 most = std::max((unsigned __int128)top1 * top2, (unsigned __int128)top1 * (top1 - (top1 > 0)) / 2);
-    cell_rows = most < n_pairs ? (uint64_t)most : n_pairs;
-  }
-  uint64_t lds_budget = kLdsDefault;
-  if (const char *e = test_knob("GRID_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), kLdsMax);
-  // The window of a tile: the row bins that 99 of 100 tiles span (a tile may begin at any row: a chunk does).  Not the largest
-  // span: gbin counts the empty bins too, and one gap of megabases -- a centromere -- would size every tile for it.  The rows of a
-  // tile that lie beyond the window add to global memory (accumulate).
-  uint64_t tile_bins = 1;
-  if (band > 0) {
-    std::vector<uint32_t> spans(n);
-    for (uint64_t s = 0; s < n; ++s) spans[s] = gbin[std::min<uint64_t>(s + kTileRows, n) - 1] - gbin[s] + 1;
-    const auto q99 = spans.begin() + (n - 1) * 99 / 100;
-    std::nth_element(spans.begin(), q99, spans.end());
-    tile_bins = *q99;
-  }
-  const bool use_lds = band > 0 && (unsigned __int128)words * tile_bins * band * 8 <= lds_budget;
-  S.lds = use_lds ? 1 : 0;
-  const uint64_t chunk = record_chunk(test_knob("GRID_CHUNK_PAIRS"));
+    uint64_t lds_budget = kLdsDefault;
+    if (const char *e = test_knob("GRID_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), kLdsMax);
+    // The window of a tile: the row bins that 99 of 100 tiles span (a tile may begin at any row: a chunk does).  Not the largest
+    // span: gbin counts the empty bins too, and one gap of megabases -- a centromere -- would size every tile for it.  The rows of a
+    // tile that lie beyond the window add to global memory (accumulate).
+    if (band > 0) {
+      std::vector<uint32_t> spans(n);
+      for (uint64_t s = 0; s < n; ++s) spans[s] = gbin[std::min<uint64_t>(s + kTileRows, n) - 1] - gbin[s] + 1;
+      const auto q99 = spans.begin() + (n - 1) * 99 / 100;
+      std::nth_element(spans.begin(), q99, spans.end());
+      tile_bins = *q99;
+    }
+    use_lds = band > 0 && (unsigned __int128)words * tile_bins * band * 8 <= lds_budget;
+    S.lds = use_lds ? 1 : 0;
 
-  const size_t W = (size_t)words * cells;
-  std::vector<unsigned long long> h_acc(W, 0);
-  if (n_pairs > 0 && cells > 0) {
-    DevBuf<uint32_t> d_gbin;
-    DevBuf<unsigned long long> d_acc, d_meta;
-    if (const int rc = F.upload(c)) return rc;
-    HIP_TRY(c, d_gbin.resize(n));
-    HIP_TRY(c, d_acc.resize(W));
-    HIP_TRY(c, d_meta.resize(3));
-    HIP_TRY(c, hipMemcpy(d_gbin.p, gbin.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
-    HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    RecordPass R;
-    if (const int rc = R.open(c, chunk)) return rc;
-    GridArgs A{};
-    A.items = c->d_items.p;
-    A.item_off = c->d_item_off.p;
-    A.rec = R.records();
-    A.cum = F.d_cum.p;
-    A.infc = F.d_infc.p;
-    A.maf_ok = F.d_maf_ok.p;
-    A.gbin = d_gbin.p;
-    A.limit = limit;
-    A.linked_min = p->linked_min;
-    A.n_sites = (uint32_t)n;
-    A.band = (uint32_t)band;
-    A.tile_rows = kTileRows;
-    A.tile_bins = (uint32_t)tile_bins;
-    A.cells = cells;
-    A.ns = ns;
-    for (int v = 0; v < 4; ++v) A.field[v] = field[v];
-    A.abs_value = p->abs_value != 0 ? 1 : 0;
-    // every partial sum of a cell is exact while max |q| * (the rows it can hold) < 2^63: certain below 2^25 rows (|q| < 2^38)
-    A.track_max = track_sums(cell_rows >= (1ull << 25)) ? 1 : 0;
-    A.acc = d_acc.p;
-    A.meta = d_meta.p;
-    const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    const size_t lds_bytes = use_lds ? (size_t)words * tile_bins * band * 8 : 0;
-    const int rc = R.run(&S.pairs_ms, &S.grid_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
-      A.out_base = ch.out_base;
-      A.r0 = ch.r0;
-      A.r1 = ch.r1;
-      A.i0 = (uint64_t)(items - c->d_items.p);
-      A.i1 = A.i0 + n_items;
-      if (use_lds) {
-        const unsigned tiles = blocks_for(ch.r1 - ch.r0, A.tile_rows);
-        hipLaunchKernelGGL(grid_kernel<true>, dim3(tiles), dim3(256), lds_bytes, st, A);
-      } else {
-        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-        hipLaunchKernelGGL(grid_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
-      }
-    }, [&](const RecordChunk &) -> int {
+    W = (size_t)words * cells;
+    h_acc.assign(W, 0);
+    if (n_pairs > 0 && cells > 0) {
+      if (const int rc = F.upload(c)) return rc;
+      HIP_TRY(c, d_gbin.resize(n));
+      HIP_TRY(c, d_acc.resize(W));
+      HIP_TRY(c, d_meta.resize(3));
+      HIP_TRY(c, hipMemcpy(d_gbin.p, gbin.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
+      HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
+      A.items = c->d_items.p;
+      A.item_off = c->d_item_off.p;
+      A.cum = F.d_cum.p;
+      A.infc = F.d_infc.p;
+      A.maf_ok = F.d_maf_ok.p;
+      A.gbin = d_gbin.p;
+      A.limit = limit;
+      A.linked_min = p->linked_min;
+      A.n_sites = (uint32_t)n;
+      A.band = (uint32_t)band;
+      A.tile_rows = kTileRows;
+      A.tile_bins = (uint32_t)tile_bins;
+      A.cells = cells;
+      A.ns = ns;
+      for (int v = 0; v < 4; ++v) A.field[v] = field[v];
+      A.abs_value = p->abs_value != 0 ? 1 : 0;
+      // every partial sum of a cell is exact while max |q| * (the rows it can hold) < 2^63: certain below 2^25 rows (|q| < 2^38)
+      A.track_max = track_sums(cell_rows >= (1ull << 25)) ? 1 : 0;
+      A.acc = d_acc.p;
+      A.meta = d_meta.p;
+      const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
+      lds_bytes = use_lds ? (size_t)words * tile_bins * band * 8 : 0;
+      client.kernel_ms = &S.grid_ms;
+      client.launch = [this, c, st, max_blocks](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+        A.out_base = ch.out_base;
+        A.r0 = ch.r0;
+        A.r1 = ch.r1;
+        A.i0 = (uint64_t)(items - c->d_items.p);
+        A.i1 = A.i0 + n_items;
+        if (use_lds) {
+          const unsigned tiles = blocks_for(ch.r1 - ch.r0, A.tile_rows);
+          hipLaunchKernelGGL(grid_kernel<true>, dim3(tiles), dim3(256), lds_bytes, st, A);
+        } else {
+          const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+          hipLaunchKernelGGL(grid_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
+        }
+      };
+      client.after = [this, c, st](const RecordChunk &) -> int {
+        unsigned long long meta[3] = {0, 0, 0};
+        HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (meta[0] != 0) return fail_value_range(c, "grid", meta[0]);
+        if (meta[2] != 0) return fail(c, NGSLD_ERR_INVALID, "LD grid: a pair beyond the band of its row (internal error)");
+        return NGSLD_OK;
+      };
+    }
+    return NGSLD_OK;
+  }
+
+  void bind(ngsld_rec_std *records) override { A.rec = records; }
+
+  int finish(ngsld_ctx *c, const RecordPass::Shared &shared) override {
+    hipStream_t st = c->stream;
+    if (client.launch) {
+      S.pairs_ms = shared.pairs_ms;
+      S.chunks = shared.chunks;
       unsigned long long meta[3] = {0, 0, 0};
+      HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
-      if (meta[0] != 0) return fail_value_range(c, "grid", meta[0]);
-      if (meta[2] != 0) return fail(c, NGSLD_ERR_INVALID, "LD grid: a pair beyond the band of its row (internal error)");
-      return NGSLD_OK;
-    });
-    if (rc != NGSLD_OK) return rc;
-    unsigned long long meta[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (A.track_max && sum_may_wrap(meta[1], cell_rows))
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "a grid cell of up to " + std::to_string(cell_rows) + " pairs with values too large to sum exactly");
-  }
+      if (A.track_max && sum_may_wrap(meta[1], cell_rows))
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a grid cell of up to " + std::to_string(cell_rows) + " pairs with values too large to sum exactly");
+    }
 
-  // ---- the cells with rows, by chromosome, b1, b2 (the order of the words): exact integer sums, one rounding for the mean ----
-  ngsld_ctx::Grid &G = c->grid;
-  for (const Chr &ch : chrs) G.chr_name.push_back(ch.name);
-  uint64_t n_cells = 0;
-  for (uint64_t w = 0; w < cells; ++w) n_cells += h_acc[w] != 0;
-  G.chr.reserve(n_cells);
-  G.b1.reserve(n_cells);
-  G.b2.reserve(n_cells);
-  G.n.reserve(n_cells);
-  size_t ci = 0;
-  for (uint64_t g = 0; g < n_bins && band > 0; ++g) {
-    while (ci + 1 < chrs.size() && chrs[ci + 1].gbin0 <= g) ++ci;
-    const uint64_t b1 = chrs[ci].first_bin + (g - chrs[ci].gbin0);
-    for (uint64_t k = 0; k < band; ++k) {
-      const uint64_t rows = h_acc[g * band + k];
-      if (rows == 0) continue;
-      G.chr.push_back((uint32_t)ci);
-      G.b1.push_back(b1);
-      G.b2.push_back(b1 + k);
-      G.n.push_back(rows);
-      S.pairs_counted += rows;
+    // ---- the cells with rows, by chromosome, b1, b2 (the order of the words): exact integer sums, one rounding for the mean ----
+    ngsld_ctx::Grid &G = c->grid;
+    for (const Chr &ch : chrs) G.chr_name.push_back(ch.name);
+    uint64_t n_cells = 0;
+    for (uint64_t w = 0; w < cells; ++w) n_cells += h_acc[w] != 0;
+    G.chr.reserve(n_cells);
+    G.b1.reserve(n_cells);
+    G.b2.reserve(n_cells);
+    G.n.reserve(n_cells);
+    size_t ci = 0;
+    for (uint64_t g = 0; g < n_bins && band > 0; ++g) {
+      while (ci + 1 < chrs.size() && chrs[ci + 1].gbin0 <= g) ++ci;
+      const uint64_t b1 = chrs[ci].first_bin + (g - chrs[ci].gbin0);
+      for (uint64_t k = 0; k < band; ++k) {
+        const uint64_t rows = h_acc[g * band + k];
+        if (rows == 0) continue;
+        G.chr.push_back((uint32_t)ci);
+        G.b1.push_back(b1);
+        G.b2.push_back(b1 + k);
+        G.n.push_back(rows);
+        S.pairs_counted += rows;
+      }
     }
-  }
-  G.sum.resize((size_t)ns * n_cells);
-  G.max.resize((size_t)ns * n_cells);
-  G.linked.resize((size_t)ns * n_cells);
-  G.mean.resize((size_t)ns * n_cells);
-  for (int v = 0; v < ns; ++v) {
-    size_t k = (size_t)v * n_cells;
-    for (uint64_t w = 0; w < cells; ++w) {
-      if (h_acc[w] == 0) continue;
-      const FieldSummary f = field_summary(h_acc.data(), cells, v, w);
-      G.sum[k] = f.sum;
-      G.max[k] = f.max;
-      G.linked[k] = f.linked;
-      G.mean[k] = f.mean;
-      ++k;
+    G.sum.resize((size_t)ns * n_cells);
+    G.max.resize((size_t)ns * n_cells);
+    G.linked.resize((size_t)ns * n_cells);
+    G.mean.resize((size_t)ns * n_cells);
+    for (int v = 0; v < ns; ++v) {
+      size_t k = (size_t)v * n_cells;
+      for (uint64_t w = 0; w < cells; ++w) {
+        if (h_acc[w] == 0) continue;
+        const FieldSummary f = field_summary(h_acc.data(), cells, v, w);
+        G.sum[k] = f.sum;
+        G.max[k] = f.max;
+        G.linked[k] = f.linked;
+        G.mean[k] = f.mean;
+        ++k;
+      }
     }
+    G.fields = p->fields;
+    S.cells = n_cells;
+    S.total_ms = ms_since(t_all);
+    copy_stats(stats, S);
+    return NGSLD_OK;
   }
-  G.fields = p->fields;
-  S.cells = n_cells;
-  S.total_ms = ms_since(t_all);
-  copy_stats(stats, S);
-  return NGSLD_OK;
+};
+
+}  // namespace
+
+namespace ngsld {
+namespace eng {
+std::unique_ptr<AnalysisPass> make_grid_pass(const ngsld_grid_params *p, const char *const *labels, ngsld_grid_stats *stats) {
+  return std::unique_ptr<AnalysisPass>(new GridPass(p, labels, stats));
+}
+}  // namespace eng
+}  // namespace ngsld
+
+extern "C" {
+
+int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labels, ngsld_grid_stats *stats) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  GridPass pass(p, labels, stats);
+  return run_single(c, pass, record_chunk(test_knob("GRID_CHUNK_PAIRS")));
 } NGSLD_CATCH(c)
 
 int ngsld_grid_cells(ngsld_ctx *c, uint64_t cap, uint32_t *chr, uint64_t *bin1, uint64_t *bin2, uint64_t *n, uint64_t *n_cells) {

@@ -17,7 +17,7 @@
 //   PRUNE_HOST_AFTER, DECAY_LDS_BYTES, DECAY_CHUNK_PAIRS, BLOCKS_CHUNK_PAIRS, BLOCKS_HOST_ROWS, BLOCKS_TEXT_ROWS,
 //   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS, GRID_LDS_BYTES, GRID_CHUNK_PAIRS,
 //   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST, SCAN_CHUNK_PAIRS, SCAN_PLANT_DP,
-//   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT,
+//   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT, ANALYZE_CHUNK_PAIRS,
 //   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS
 // LINKED_FORCE_HOST=1: every chunk of ngsld_linked_pairs takes the host formatter, as BLOCKS_HOST_ROWS does for the block matrices.
 // SCAN_PLANT_DP=R:X: record R of the plan gets D' = X in ngsld_scan's record buffer before its kernel reads it (scan.hip) -- no input
@@ -26,6 +26,7 @@
 // tests/test_gpu_record_pass_large.py holds them to the passes' rules: ngsld_prune's chunk loop (its edge arrays regrown and its
 // edge count carried from chunk to chunk; a row that does not fit the record buffer), a chunk's items cut into several launches
 // (2^24 items otherwise), and the guard of the integer sums (max |q| tracked from 2^25 rows on, refused from 2^63 on).
+// ANALYZE_CHUNK_PAIRS: the chunk of ngsld_analyze (analyze.hip), which does not read the single calls' *_CHUNK_PAIRS.
 // FIRST_STEP=0: the run kernel takes no pair's first EM step from the sites' dosages (ld_kernel_run.h) -- every pair starts at
 // iteration 0 with the per-individual step, and the records are what they were before that step existed (A/B, tests).
 // PAIR_MOMENTS=0: no pair_ld_moments_kernel in front of the run kernel (engine_run.hip, timed_launch) -- the kernel forms each pair's

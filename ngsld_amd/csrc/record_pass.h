@@ -5,8 +5,12 @@
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
 // linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ.
 // (ngsld_scan uses the site filter, the chunk loop, the two refusals and the guard of the sums.)
+// The chunk loop takes a list of passes: the pairs of a chunk run once and every pass of the list reads them (ngsld_analyze,
+// analyze.hip); the six passes it can list are AnalysisPass objects, and their single calls are a list of one.
 // Host code; the definitions are in record_pass.hip.
 #pragma once
+
+#include <memory>
 
 #include "engine.h"
 #include "ld_records.h"
@@ -77,26 +81,43 @@ struct RecordChunk {
   uint64_t r0, r1, pairs, out_base;
 };
 
-// The rows of a pass, chunk by chunk, through the pair kernels into a record buffer of its own, and the pass's kernel over each
-// chunk's items.
+// The rows of one or several passes, chunk by chunk, through the pair kernels -- once -- into one record buffer, and every
+// pass's kernel over each chunk's items.
 struct RecordPass {
   // launch(chunk, items, n_items): the pass's kernel over one slice of the chunk's items (device pointer)
   using Launch = std::function<void(const RecordChunk &, const ngsld_item *items, uint64_t n_items)>;
   // before(chunk): the chunk's records are final, nothing of the pass is launched yet (outside the events);
   // after(chunk): once the chunk's launches are done (the next chunk's pairs overwrite the records)
   using Step = std::function<int(const RecordChunk &)>;
+  // A pass as the chunk loop sees it: its three hooks, where its kernel time goes, and the events that bracket its launches.
+  // A client without a launch has nothing to read (a pass with no bin to fill): the loop passes it by.
+  struct Client {
+    Step before;
+    Launch launch;
+    Step after;
+    double *kernel_ms = nullptr;  // where the span of its events adds (a field of its stats)
+    double kernel_total_ms = 0;   // the same span, for the list's total
+    EventPair ev;
+  };
+  // what the clients share: the wall time of the pair phase, the chunks, the pairs handed to ngsld_run_device
+  struct Shared {
+    double pairs_ms = 0;
+    uint64_t chunks = 0, pairs_run = 0;
+  };
 
-  // The record buffer and the events.  The rows: every row, or the rows s with rows[s] != 0 (it must outlive run).  Chunks of
+  // The record buffer.  The rows: every row, or the rows s with rows[s] != 0 (it must outlive run).  Chunks of
   // consecutive rows of up to chunk_pairs records; a row is never cut, so the buffer holds the chunk (at most the rows' pairs)
   // or the longest row where that is longer -- or, with fit_longest_row false, just chunk_pairs records: a longer row is refused
   // in run ("a row of N pairs does not fit the record buffer").  with_ext: a second buffer of as many 40 B records, which the pair
   // kernels fill as the plan's extend_out has them (ngsld_linked_pairs prints them).
   int open(ngsld_ctx *c, uint64_t chunk_pairs, const uint8_t *rows = nullptr, bool fit_longest_row = true, bool with_ext = false);
-  // Every chunk: ngsld_run_device + ngsld_finish_device on the context's stream, so every record is final (replayed pairs carry
-  // their replayed values); before; launch for each slice of the chunk's items, every slice below 2^32 threads at one wavefront
-  // per item (2^24 items, or NGSLD_TEST_RECORD_SLICE_ITEMS if that is fewer), all of them between two events; the wait for the
-  // second; then after.  *pairs_ms adds the wall time of the pair phase, *kernel_ms the events' span, *chunks (when not null)
-  // counts the chunks.
+  // Every chunk: ngsld_run_device + ngsld_finish_device on the context's stream, once, so every record is final (replayed pairs
+  // carry their replayed values); then the clients in list order, each: its before; its launch for each slice of the chunk's
+  // items, every slice below 2^32 threads at one wavefront per item (2^24 items, or NGSLD_TEST_RECORD_SLICE_ITEMS if that is
+  // fewer), all of them between its two events; the wait for the second, whose span adds to its kernel_ms; then its after.
+  // Nothing runs when no client has a launch.  *shared (when not null) adds the pair phase's wall time, chunks and pairs.
+  int run(Client *const *clients, size_t n_clients, Shared *shared);
+  // a list of one, from its parts (ngsld_blocks, ngsld_linked_pairs)
   int run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const Step &before, const Launch &launch, const Step &after = nullptr);
   ngsld_rec_std *records() const { return d_rec.p; }
   ngsld_rec_ext *ext_records() const { return d_ext.p; }  // null unless opened with_ext
@@ -111,8 +132,38 @@ struct RecordPass {
   const uint8_t *rows = nullptr;
   DevBuf<ngsld_rec_std> d_rec;
   DevBuf<ngsld_rec_ext> d_ext;
-  EventPair ev;
 };
+
+// ---- a pass in four parts ----
+// ngsld_prune, ngsld_decay, ngsld_site_ld, ngsld_clusters, ngsld_grid and ngsld_scan are each one object of this shape, so that
+// the single calls and ngsld_analyze (analyze.hip) drive the same code: run_passes below over a list of one, or of several.
+struct AnalysisPass {
+  RecordPass::Client client;
+  virtual ~AnalysisPass() = default;
+  // the parameters (host only, no device is touched): the single call's codes and messages
+  virtual int validate(ngsld_ctx *c) = 0;
+  // the context's store of this kind, emptied: its getters answer as before any call
+  virtual void clear(ngsld_ctx *c) = 0;
+  // the site arrays, the device buffers and their uploads, the track_* decisions, the hooks of `client`; chunk_pairs is the
+  // chunk the records will come in
+  virtual int prepare(ngsld_ctx *c, uint64_t chunk_pairs) = 0;
+  // false: the record buffer holds chunk_pairs records and a longer row is refused (pruning)
+  virtual bool fit_longest_row() const { return true; }
+  // the record buffer, open now, that the hooks read
+  virtual void bind(ngsld_rec_std *records) = 0;
+  // the copy back, the guards of the sums, the store in the context, the stats (the record buffer is closed by now)
+  virtual int finish(ngsld_ctx *c, const RecordPass::Shared &shared) = 0;
+};
+// prepare each, one RecordPass over all their clients, finish each; the first failure ends it
+int run_passes(ngsld_ctx *c, AnalysisPass *const *passes, size_t n, uint64_t chunk_pairs, RecordPass::Shared *shared);
+// a single call: validate, then a list of one
+int run_single(ngsld_ctx *c, AnalysisPass &pass, uint64_t chunk_pairs);
+std::unique_ptr<AnalysisPass> make_prune_pass(const ngsld_prune_params *p, const char *const *labels, uint8_t *site_state, ngsld_prune_stats *stats);
+std::unique_ptr<AnalysisPass> make_decay_pass(const ngsld_decay_params *p, ngsld_decay_stats *stats);
+std::unique_ptr<AnalysisPass> make_site_ld_pass(const ngsld_site_ld_params *p, ngsld_site_ld_stats *stats);
+std::unique_ptr<AnalysisPass> make_clusters_pass(const ngsld_clusters_params *p, ngsld_clusters_stats *stats);
+std::unique_ptr<AnalysisPass> make_grid_pass(const ngsld_grid_params *p, const char *const *labels, ngsld_grid_stats *stats);
+std::unique_ptr<AnalysisPass> make_scan_pass(const ngsld_scan_params *p, ngsld_scan_stats *stats);
 
 // ---- what the entries share ----
 // the refusals every pass makes once its own parameters have passed, the device, the zeroed stats

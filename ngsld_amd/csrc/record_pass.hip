@@ -50,12 +50,42 @@ int RecordPass::open(ngsld_ctx *ctx, uint64_t chunk, const uint8_t *only_rows, b
   }
   HIP_TRY(c, d_rec.resize(cap));
   if (with_ext) HIP_TRY(c, d_ext.resize(cap));
-  HIP_TRY(c, ev.create());
   return NGSLD_OK;
 }
 
 int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const Step &before, const Launch &launch, const Step &after) {
+  Client one;
+  one.before = before;
+  one.launch = launch;
+  one.after = after;
+  one.kernel_ms = kernel_ms;
+  Client *const list[1] = {&one};
+  Shared sh;
+  const int rc = run(list, 1, &sh);
+  if (pairs_ms) *pairs_ms += sh.pairs_ms;
+  if (chunks) *chunks += sh.chunks;
+  return rc;
+}
+
+int RecordPass::run(Client *const *clients, size_t n_clients, Shared *shared) {
   const uint64_t n = c->n_sites;
+  bool any = false;
+  for (size_t k = 0; k < n_clients; ++k) {
+    if (!clients[k]->launch) continue;
+    any = true;
+    if (clients[k]->ev.a == nullptr) HIP_TRY(c, clients[k]->ev.create());
+  }
+  if (!any) return NGSLD_OK;
+  Shared sh;
+  struct Report {  // (a failure reports the pairs that ran before it too)
+    Shared *out, *sh;
+    ~Report() {
+      if (out == nullptr) return;
+      out->pairs_ms += sh->pairs_ms;
+      out->chunks += sh->chunks;
+      out->pairs_run += sh->pairs_run;
+    }
+  } report{shared, &sh};
   // The records are read as printed (ld_prune.h): the launches flag, and the replay settles, the pairs whose sixth decimal
   // or sign rounding noise could change, as for text output -- a D one ulp off an odd / 128 tie would quantise to the other
   // neighbour than the reference's "%f"
@@ -77,33 +107,71 @@ int RecordPass::run(double *pairs_ms, double *kernel_ms, uint64_t *chunks, const
     if (ch.pairs > d_rec.n) return fail(c, NGSLD_ERR_UNSUPPORTED, "a row of " + std::to_string(ch.pairs) + " pairs does not fit the record buffer");
     if (ch.pairs > 0) {
       const auto t0 = std::chrono::steady_clock::now();
+      sh.pairs_run += ch.pairs;
       int rc = ngsld_run_device(c, r0, r1, d_rec.p, d_ext.p, nullptr);  // (the ctx's stream: records final, replay done)
       if (rc == NGSLD_OK) rc = ngsld_finish_device(c);
       if (rc != NGSLD_OK) return rc;
-      if (pairs_ms) *pairs_ms += ms_since(t0);
-      if (before) {
-        rc = before(ch);
-        if (rc != NGSLD_OK) return rc;
-      }
+      sh.pairs_ms += ms_since(t0);
+      ++sh.chunks;
       const uint64_t i0 = c->h_item_off[r0], i1 = c->h_item_off[r1];
       const uint64_t max_items = record_slice_items();
-      HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-      for (uint64_t off = i0; off < i1; off += max_items) {
-        launch(ch, c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));
-        HIP_TRY(c, hipGetLastError());
-      }
-      HIP_TRY(c, hipEventRecord(ev.b, c->stream));
-      HIP_TRY(c, hipEventSynchronize(ev.b));
-      HIP_TRY(c, ev.add_elapsed(kernel_ms));
-      if (chunks) ++*chunks;
-      if (after) {
-        rc = after(ch);
-        if (rc != NGSLD_OK) return rc;
+      for (size_t k = 0; k < n_clients; ++k) {
+        Client &cl = *clients[k];
+        if (!cl.launch) continue;
+        if (cl.before) {
+          rc = cl.before(ch);
+          if (rc != NGSLD_OK) return rc;
+        }
+        HIP_TRY(c, hipEventRecord(cl.ev.a, c->stream));
+        for (uint64_t off = i0; off < i1; off += max_items) {
+          cl.launch(ch, c->d_items.p + off, std::min<uint64_t>(max_items, i1 - off));
+          HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipEventRecord(cl.ev.b, c->stream));
+        HIP_TRY(c, hipEventSynchronize(cl.ev.b));
+        double span = 0;
+        HIP_TRY(c, cl.ev.add_elapsed(&span));
+        cl.kernel_total_ms += span;
+        if (cl.kernel_ms) *cl.kernel_ms += span;
+        if (cl.after) {
+          rc = cl.after(ch);
+          if (rc != NGSLD_OK) return rc;
+        }
       }
     }
     r0 = r1;
   }
   return NGSLD_OK;
+}
+
+int run_passes(ngsld_ctx *c, AnalysisPass *const *passes, size_t n, uint64_t chunk_pairs, RecordPass::Shared *shared) {
+  RecordPass::Shared sh;
+  bool any = false, fit = true;
+  std::vector<RecordPass::Client *> clients;
+  for (size_t k = 0; k < n; ++k) {
+    if (const int rc = passes[k]->prepare(c, chunk_pairs)) return rc;
+    any = any || passes[k]->client.launch;
+    fit = fit && passes[k]->fit_longest_row();
+    clients.push_back(&passes[k]->client);
+  }
+  if (any) {
+    RecordPass R;
+    const uint64_t n_pairs = c->h_row_off[c->n_sites];
+    if (const int rc = R.open(c, fit ? chunk_pairs : std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, chunk_pairs)), nullptr, fit)) return rc;
+    for (size_t k = 0; k < n; ++k) passes[k]->bind(R.records());
+    const int rc = R.run(clients.data(), n, &sh);
+    if (shared) *shared = sh;
+    if (rc != NGSLD_OK) return rc;
+  }  // (the records go before the finishes: pruning builds its graph in their room)
+  for (size_t k = 0; k < n; ++k)
+    if (const int rc = passes[k]->finish(c, sh)) return rc;
+  return NGSLD_OK;
+}
+
+int run_single(ngsld_ctx *c, AnalysisPass &pass, uint64_t chunk_pairs) {
+  if (const int rc = pass.validate(c)) return rc;
+  AnalysisPass *const list[1] = {&pass};
+  return run_passes(c, list, 1, chunk_pairs, nullptr);
 }
 
 int fail_value_range(ngsld_ctx *c, const char *pass, unsigned long long meta0) {

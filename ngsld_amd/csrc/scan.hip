@@ -152,177 +152,227 @@ __global__ __launch_bounds__(256) void scan_kernel(ScanArgs A) {
   }
 }
 
+// ngsld_scan in four parts (record_pass.h AnalysisPass)
+struct ScanPass final : AnalysisPass {
+  const ngsld_scan_params *p;
+  ngsld_scan_stats *stats;
+  const std::chrono::steady_clock::time_point t_all = std::chrono::steady_clock::now();
+  ngsld_scan_stats S;
+  SiteFilter F;
+  int field[4] = {0, 0, 0, 0};
+  int ns = 0;
+  uint32_t words = 0;
+  std::vector<uint32_t> win_a, win_b;
+  uint64_t rows_max = 0;
+  bool track = false;
+  size_t n1 = 0, W = 0;
+  std::vector<unsigned long long> h_acc;
+  DevBuf<unsigned long long> d_acc, d_sum, d_meta;
+  DevBuf<uint32_t> d_a, d_b;
+  ScanArgs A{};
+  ngsld_rec_std *rec = nullptr;
+  uint64_t plant_at = ~0ull;
+  double plant_dp = 0.0;
+
+  ScanPass(const ngsld_scan_params *params, ngsld_scan_stats *out) : p(params), stats(out) {}
+
+  int validate(ngsld_ctx *c) override {
+    if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+    if (const int rc = check_struct_sizes(c, p, "ngsld_scan_params", stats, "ngsld_scan_stats")) return rc;
+    if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "scan fields must be a non-empty mask of 1, 2, 4, 8");
+    if (p->half_window >= (1ull << 31)) return fail(c, NGSLD_ERR_INVALID, "scan half_window must be below 2^31");
+    if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "scan max_kb_dist must be >= 0");
+    if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "scan min_maf is NaN");
+    // a window holds the site pairs up to 2 H apart: a plan that stops short of them would leave a window's mean without rows
+    // the TSV never had, silently
+    if (c->params.max_kb_dist > 0 && c->params.max_kb_dist * 1000 < 2 * p->half_window)
+      return fail(c, NGSLD_ERR_INVALID, "scan half_window " + std::to_string(p->half_window) + " needs the pairs up to " +
+                                            std::to_string(2 * p->half_window) + " bp apart: the plan's max_kb_dist holds them up to " +
+                                            std::to_string(c->params.max_kb_dist * 1000) + " bp");
+    return NGSLD_OK;
+  }
+
+  void clear(ngsld_ctx *c) override { c->clear_scan(); }
+
+  int prepare(ngsld_ctx *c, uint64_t) override {
+    const uint64_t n = c->n_sites;
+    if (const int rc = begin_pass(c, S)) return rc;
+    if (n >= 0x7fffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "scan needs n_sites below 2^31 - 1");
+    clear(c);
+    hipStream_t st = c->stream;
+    ns = field_list(p->fields, field);
+    words = 1u + (uint32_t)ns;
+
+    // ---- sites: the dist prefix sums, the maf filter on the printed maf, the windows ----
+    const double limit = p->max_kb_dist * 1000.0;
+    F.prepare(c, &p->min_maf);
+    if (!F.exact_gaps) return fail(c, NGSLD_ERR_UNSUPPORTED, "scan needs integer position gaps");
+    win_a.resize(n);
+    win_b.resize(n);
+    uint64_t largest = 0;
+    {
+      const double H = (double)p->half_window;
+      uint64_t lo = 0, hi = 0;  // both only move forward: cum does not decrease inside a chromosome
+      for (uint64_t s = 0; s < n; ++s) {
+        while (F.infc[lo] != F.infc[s] || F.cum[s] - F.cum[lo] > H) ++lo;
+        if (hi < s) hi = s;
+        while (hi + 1 < n && F.infc[hi + 1] == F.infc[s] && F.cum[hi + 1] - F.cum[s] <= H) ++hi;
+        win_a[s] = (uint32_t)lo;
+        win_b[s] = (uint32_t)hi;
+        largest = std::max<uint64_t>(largest, hi - lo + 1);
+      }
+    }
+    S.largest_window = largest;
+    // every partial sum of a window is exact while max |q| * (the rows it can hold) < 2^63: certain below 2^25 rows (|q| < 2^38)
+    rows_max = largest * (largest - (largest > 0 ? 1 : 0)) / 2;
+    track = track_sums(rows_max >= (1ull << 25));
+
+    const uint64_t n_pairs = c->h_row_off[n];
+    S.pairs = n_pairs;
+    n1 = (size_t)n + 1;
+    W = (size_t)3 * words * n1;
+    h_acc.assign(W, 0);
+    if (n_pairs > 0) {
+      if (const int rc = F.upload(c)) return rc;
+      HIP_TRY(c, d_a.resize(n));
+      HIP_TRY(c, d_b.resize(n));
+      HIP_TRY(c, hipMemcpy(d_a.p, win_a.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(d_b.p, win_b.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(c, d_acc.resize(W));
+      HIP_TRY(c, d_sum.resize(W));
+      HIP_TRY(c, d_meta.resize(3));
+      HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
+      HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
+      A.cum = F.d_cum.p;
+      A.infc = F.d_infc.p;
+      A.maf_ok = F.d_maf_ok.p;
+      A.win_a = d_a.p;
+      A.win_b = d_b.p;
+      A.limit = limit;
+      A.n_sites = (uint32_t)n;
+      A.ns = ns;
+      for (int v = 0; v < 4; ++v) A.field[v] = field[v];
+      A.track_max = track ? 1 : 0;
+      A.acc = d_acc.p;
+      A.meta = d_meta.p;
+      const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
+      // NGSLD_TEST_SCAN_PLANT_DP = "R:X" (tests): record R of the plan gets D' = X once its chunk's records are final.  Valid
+      // haplotype frequencies give no finite D' near 2^38 micro-units, so this is the only way to the refusal of such a value
+      // (and to a sum that holds the largest value allowed)
+      if (const char *e = test_knob("SCAN_PLANT_DP")) {
+        char *colon = nullptr;
+        const uint64_t at = std::strtoull(e, &colon, 10);
+        if (colon != e && *colon == ':') {
+          plant_at = at;
+          plant_dp = std::strtod(colon + 1, nullptr);
+        }
+      }
+      const RecordPass::Step plant = [this, c, st](const RecordChunk &ch) -> int {
+        if (plant_at < ch.out_base || plant_at - ch.out_base >= ch.pairs) return NGSLD_OK;
+        HIP_TRY(c, hipMemcpyAsync(&rec[plant_at - ch.out_base].Dp, &plant_dp, sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        return NGSLD_OK;
+      };
+      client.kernel_ms = &S.scan_ms;
+      if (plant_at != ~0ull) client.before = plant;
+      client.launch = [this, st, max_blocks](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+        A.out_base = ch.out_base;
+        A.items = items;
+        A.n_items = n_items;
+        const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
+        hipLaunchKernelGGL(scan_kernel, dim3(blocks), dim3(256), 0, st, A);
+      };
+      client.after = [this, c, st](const RecordChunk &) -> int {
+        unsigned long long bad = 0;
+        HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        return bad != 0 ? fail_value_range(c, "scan", bad) : NGSLD_OK;
+      };
+    }
+    return NGSLD_OK;
+  }
+
+  void bind(ngsld_rec_std *records) override {
+    A.rec = records;
+    rec = records;
+  }
+
+  int finish(ngsld_ctx *c, const RecordPass::Shared &shared) override {
+    const uint64_t n = c->n_sites;
+    hipStream_t st = c->stream;
+    if (client.launch) {
+      S.pairs_ms = shared.pairs_ms;
+      S.chunks = shared.chunks;
+      // ---- the differences become the windows' totals: one inclusive sum per array, wrapping ----
+      EventPair ev;
+      HIP_TRY(c, ev.create());
+      size_t temp_bytes = 0;
+      HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, temp_bytes, d_acc.p, d_sum.p, (int)n1, st));
+      DevBuf<char> d_temp;
+      HIP_TRY(c, d_temp.resize(std::max<size_t>(temp_bytes, 1)));
+      HIP_TRY(c, hipEventRecord(ev.a, st));
+      for (size_t k = 0; k < (size_t)3 * words; ++k)
+        HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(d_temp.p, temp_bytes, d_acc.p + k * n1, d_sum.p + k * n1, (int)n1, st));
+      HIP_TRY(c, hipEventRecord(ev.b, st));
+      unsigned long long meta[3] = {0, 0, 0};
+      HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_sum.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      HIP_TRY(c, ev.add_elapsed(&S.scan_ms));
+      S.pairs_counted = meta[2];
+      if (track && sum_may_wrap(meta[1], rows_max))
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a window of up to " + std::to_string(rows_max) + " pairs with values too large to sum exactly");
+    }
+
+    // ---- per site: exact integer sums, one rounding each for zns and omega ----
+    ngsld_ctx::Scan &R = c->scan;
+    R.first = std::move(win_a);
+    R.last = std::move(win_b);
+    R.n.resize(3 * n);
+    R.sum.resize((size_t)ns * 3 * n);
+    R.zns.resize((size_t)ns * n);
+    R.omega.resize((size_t)ns * n);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint64_t s = 0; s < n; ++s) {
+      uint64_t cnt[3];
+      for (int k = 0; k < 3; ++k) cnt[k] = R.n[(size_t)k * n + s] = h_acc[(size_t)k * words * n1 + s];
+      const uint64_t rows = cnt[kLL] + cnt[kRR] + cnt[kLR], inside = cnt[kLL] + cnt[kRR];
+      for (int v = 0; v < ns; ++v) {
+        uint64_t sum[3];
+        for (int k = 0; k < 3; ++k) {
+          sum[k] = h_acc[((size_t)k * words + 1 + v) * n1 + s];
+          R.sum[((size_t)v * 3 + k) * n + s] = (int64_t)sum[k];
+        }
+        const size_t at = (size_t)v * n + s;
+        R.zns[at] = rows > 0 ? mean_nearest(sum[kLL] + sum[kRR] + sum[kLR], rows) : nan;
+        R.omega[at] = (inside > 0 && cnt[kLR] > 0 && sum[kLR] > 0)
+                          ? ratio_nearest((unsigned __int128)(sum[kLL] + sum[kRR]) * cnt[kLR], (unsigned __int128)inside * sum[kLR])
+                          : nan;
+      }
+    }
+    R.fields = p->fields;
+    S.total_ms = ms_since(t_all);
+    copy_stats(stats, S);
+    return NGSLD_OK;
+  }
+};
+
 }  // namespace
+
+namespace ngsld {
+namespace eng {
+std::unique_ptr<AnalysisPass> make_scan_pass(const ngsld_scan_params *p, ngsld_scan_stats *stats) {
+  return std::unique_ptr<AnalysisPass>(new ScanPass(p, stats));
+}
+}  // namespace eng
+}  // namespace ngsld
 
 extern "C" {
 
 int ngsld_scan(ngsld_ctx *c, const ngsld_scan_params *p, ngsld_scan_stats *stats) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  const auto t_all = std::chrono::steady_clock::now();
-  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (const int rc = check_struct_sizes(c, p, "ngsld_scan_params", stats, "ngsld_scan_stats")) return rc;
-  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "scan fields must be a non-empty mask of 1, 2, 4, 8");
-  if (p->half_window >= (1ull << 31)) return fail(c, NGSLD_ERR_INVALID, "scan half_window must be below 2^31");
-  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "scan max_kb_dist must be >= 0");
-  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "scan min_maf is NaN");
-  // a window holds the site pairs up to 2 H apart: a plan that stops short of them would leave a window's mean without rows
-  // the TSV never had, silently
-  if (c->params.max_kb_dist > 0 && c->params.max_kb_dist * 1000 < 2 * p->half_window)
-    return fail(c, NGSLD_ERR_INVALID, "scan half_window " + std::to_string(p->half_window) + " needs the pairs up to " +
-                                          std::to_string(2 * p->half_window) + " bp apart: the plan's max_kb_dist holds them up to " +
-                                          std::to_string(c->params.max_kb_dist * 1000) + " bp");
-  const uint64_t n = c->n_sites;
-  ngsld_scan_stats S;
-  if (const int rc = begin_pass(c, S)) return rc;
-  if (n >= 0x7fffffffull) return fail(c, NGSLD_ERR_UNSUPPORTED, "scan needs n_sites below 2^31 - 1");
-  c->clear_scan();
-  hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0};
-  const int ns = field_list(p->fields, field);
-  const uint32_t words = 1u + (uint32_t)ns;
-
-  // ---- sites: the dist prefix sums, the maf filter on the printed maf, the windows ----
-  const double limit = p->max_kb_dist * 1000.0;
-  SiteFilter F;
-  F.prepare(c, &p->min_maf);
-  if (!F.exact_gaps) return fail(c, NGSLD_ERR_UNSUPPORTED, "scan needs integer position gaps");
-  std::vector<uint32_t> win_a(n), win_b(n);
-  uint64_t largest = 0;
-  {
-    const double H = (double)p->half_window;
-    uint64_t lo = 0, hi = 0;  // both only move forward: cum does not decrease inside a chromosome
-    for (uint64_t s = 0; s < n; ++s) {
-      while (F.infc[lo] != F.infc[s] || F.cum[s] - F.cum[lo] > H) ++lo;
-      if (hi < s) hi = s;
-      while (hi + 1 < n && F.infc[hi + 1] == F.infc[s] && F.cum[hi + 1] - F.cum[s] <= H) ++hi;
-      win_a[s] = (uint32_t)lo;
-      win_b[s] = (uint32_t)hi;
-      largest = std::max<uint64_t>(largest, hi - lo + 1);
-    }
-  }
-  S.largest_window = largest;
-  // every partial sum of a window is exact while max |q| * (the rows it can hold) < 2^63: certain below 2^25 rows (|q| < 2^38)
-  const uint64_t rows_max = largest * (largest - (largest > 0 ? 1 : 0)) / 2;
-  const bool track = track_sums(rows_max >= (1ull << 25));
-  const uint64_t chunk = record_chunk(test_knob("SCAN_CHUNK_PAIRS"));
-
-  const uint64_t n_pairs = c->h_row_off[n];
-  S.pairs = n_pairs;
-  const size_t n1 = (size_t)n + 1, W = (size_t)3 * words * n1;
-  std::vector<unsigned long long> h_acc(W, 0);
-  if (n_pairs > 0) {
-    DevBuf<unsigned long long> d_acc, d_sum, d_meta;
-    DevBuf<uint32_t> d_a, d_b;
-    if (const int rc = F.upload(c)) return rc;
-    HIP_TRY(c, d_a.resize(n));
-    HIP_TRY(c, d_b.resize(n));
-    HIP_TRY(c, hipMemcpy(d_a.p, win_a.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_b.p, win_b.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, d_acc.resize(W));
-    HIP_TRY(c, d_sum.resize(W));
-    HIP_TRY(c, d_meta.resize(3));
-    HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
-    HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 3 * sizeof(unsigned long long), st));
-    RecordPass R;
-    if (const int rc = R.open(c, chunk)) return rc;
-    ScanArgs A{};
-    A.rec = R.records();
-    A.cum = F.d_cum.p;
-    A.infc = F.d_infc.p;
-    A.maf_ok = F.d_maf_ok.p;
-    A.win_a = d_a.p;
-    A.win_b = d_b.p;
-    A.limit = limit;
-    A.n_sites = (uint32_t)n;
-    A.ns = ns;
-    for (int v = 0; v < 4; ++v) A.field[v] = field[v];
-    A.track_max = track ? 1 : 0;
-    A.acc = d_acc.p;
-    A.meta = d_meta.p;
-    const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
-    // NGSLD_TEST_SCAN_PLANT_DP = "R:X" (tests): record R of the plan gets D' = X once its chunk's records are final.  Valid
-    // haplotype frequencies give no finite D' near 2^38 micro-units, so this is the only way to the refusal of such a value
-    // (and to a sum that holds the largest value allowed)
-    uint64_t plant_at = ~0ull;
-    double plant_dp = 0.0;
-    if (const char *e = test_knob("SCAN_PLANT_DP")) {
-      char *colon = nullptr;
-      const uint64_t at = std::strtoull(e, &colon, 10);
-      if (colon != e && *colon == ':') {
-        plant_at = at;
-        plant_dp = std::strtod(colon + 1, nullptr);
-      }
-    }
-    const RecordPass::Step plant = [&](const RecordChunk &ch) -> int {
-      if (plant_at < ch.out_base || plant_at - ch.out_base >= ch.pairs) return NGSLD_OK;
-      HIP_TRY(c, hipMemcpyAsync(&R.records()[plant_at - ch.out_base].Dp, &plant_dp, sizeof(double), hipMemcpyHostToDevice, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      return NGSLD_OK;
-    };
-    const int rc = R.run(&S.pairs_ms, &S.scan_ms, &S.chunks, plant_at != ~0ull ? plant : RecordPass::Step(nullptr), [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
-      A.out_base = ch.out_base;
-      A.items = items;
-      A.n_items = n_items;
-      const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
-      hipLaunchKernelGGL(scan_kernel, dim3(blocks), dim3(256), 0, st, A);
-    }, [&](const RecordChunk &) -> int {
-      unsigned long long bad = 0;
-      HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      return bad != 0 ? fail_value_range(c, "scan", bad) : NGSLD_OK;
-    });
-    if (rc != NGSLD_OK) return rc;
-    // ---- the differences become the windows' totals: one inclusive sum per array, wrapping ----
-    EventPair ev;
-    HIP_TRY(c, ev.create());
-    size_t temp_bytes = 0;
-    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, temp_bytes, d_acc.p, d_sum.p, (int)n1, st));
-    DevBuf<char> d_temp;
-    HIP_TRY(c, d_temp.resize(std::max<size_t>(temp_bytes, 1)));
-    HIP_TRY(c, hipEventRecord(ev.a, st));
-    for (size_t k = 0; k < (size_t)3 * words; ++k)
-      HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(d_temp.p, temp_bytes, d_acc.p + k * n1, d_sum.p + k * n1, (int)n1, st));
-    HIP_TRY(c, hipEventRecord(ev.b, st));
-    unsigned long long meta[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_sum.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, ev.add_elapsed(&S.scan_ms));
-    S.pairs_counted = meta[2];
-    if (track && sum_may_wrap(meta[1], rows_max))
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "a window of up to " + std::to_string(rows_max) + " pairs with values too large to sum exactly");
-  }
-
-  // ---- per site: exact integer sums, one rounding each for zns and omega ----
-  ngsld_ctx::Scan &R = c->scan;
-  R.first = std::move(win_a);
-  R.last = std::move(win_b);
-  R.n.resize(3 * n);
-  R.sum.resize((size_t)ns * 3 * n);
-  R.zns.resize((size_t)ns * n);
-  R.omega.resize((size_t)ns * n);
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (uint64_t s = 0; s < n; ++s) {
-    uint64_t cnt[3];
-    for (int k = 0; k < 3; ++k) cnt[k] = R.n[(size_t)k * n + s] = h_acc[(size_t)k * words * n1 + s];
-    const uint64_t rows = cnt[kLL] + cnt[kRR] + cnt[kLR], inside = cnt[kLL] + cnt[kRR];
-    for (int v = 0; v < ns; ++v) {
-      uint64_t sum[3];
-      for (int k = 0; k < 3; ++k) {
-        sum[k] = h_acc[((size_t)k * words + 1 + v) * n1 + s];
-        R.sum[((size_t)v * 3 + k) * n + s] = (int64_t)sum[k];
-      }
-      const size_t at = (size_t)v * n + s;
-      R.zns[at] = rows > 0 ? mean_nearest(sum[kLL] + sum[kRR] + sum[kLR], rows) : nan;
-      R.omega[at] = (inside > 0 && cnt[kLR] > 0 && sum[kLR] > 0)
-                        ? ratio_nearest((unsigned __int128)(sum[kLL] + sum[kRR]) * cnt[kLR], (unsigned __int128)inside * sum[kLR])
-                        : nan;
-    }
-  }
-  R.fields = p->fields;
-  S.total_ms = ms_since(t_all);
-  copy_stats(stats, S);
-  return NGSLD_OK;
+  ScanPass pass(p, stats);
+  return run_single(c, pass, record_chunk(test_knob("SCAN_CHUNK_PAIRS")));
 } NGSLD_CATCH(c)
 
 int ngsld_scan_get(ngsld_ctx *c, int field, uint32_t *win_first, uint32_t *win_last, uint64_t *n_ll, uint64_t *n_rr, uint64_t *n_lr,

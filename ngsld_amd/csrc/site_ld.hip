@@ -165,74 +165,84 @@ __global__ __launch_bounds__(256) void site_kernel(SiteArgs A) {
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_stats *stats) try {
-  if (c == nullptr) return NGSLD_ERR_INVALID;
-  const auto t_all = std::chrono::steady_clock::now();
-  if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
-  if (const int rc = check_struct_sizes(c, p, "ngsld_site_ld_params", stats, "ngsld_site_ld_stats")) return rc;
-  if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "site_ld fields must be a non-empty mask of 1, 2, 4, 8");
-  if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "site_ld max_kb_dist must be >= 0");
-  if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "site_ld min_maf is NaN");
-  if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "site_ld linked_min is NaN");
-  const uint64_t n = c->n_sites;
+// ngsld_site_ld in four parts (record_pass.h AnalysisPass)
+struct SiteLdPass final : AnalysisPass {
+  const ngsld_site_ld_params *p;
+  ngsld_site_ld_stats *stats;
+  const std::chrono::steady_clock::time_point t_all = std::chrono::steady_clock::now();
   ngsld_site_ld_stats S;
-  if (const int rc = begin_pass(c, S)) return rc;
-  c->clear_sites();
-  hipStream_t st = c->stream;
-  int field[4] = {0, 0, 0, 0};
-  const int ns = field_list(p->fields, field);
-  const uint32_t words = 1u + 3u * (uint32_t)ns;
-
-  // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
-  const double limit = p->max_kb_dist * 1000.0;
   SiteFilter F;
-  F.prepare(c, &p->min_maf);
-  if (const int rc = F.check_limit(c, "site_ld", limit)) return rc;
+  int field[4] = {0, 0, 0, 0};
+  int ns = 0;
+  uint32_t words = 0;
+  uint64_t cols = 0, degree_max = 0;
+  bool use_lds = false;
+  size_t W = 0;
+  std::vector<unsigned long long> h_acc;
+  DevBuf<unsigned long long> d_acc, d_meta;
+  SiteArgs A{};
 
-  // ---- from the plan: how far a row reaches (the LDS window of a tile), how many rows a site can be in (the sums' bound) ----
-  uint64_t span = 0, degree_max = 0;
-  {
-    std::vector<int64_t> cover(n + 1, 0);  // +1 where a row's candidates begin, -1 where they end
-    for (uint64_t s = 0; s < n; ++s) {
-      if (c->h_row_off[s + 1] == c->h_row_off[s] || c->h_row_end[s] <= s + 1) continue;
-      span = std::max<uint64_t>(span, c->h_row_end[s] - s - 1);
-      ++cover[s + 1];
-      --cover[c->h_row_end[s]];
-    }
-    int64_t columns = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-      columns += cover[s];
-      degree_max = std::max<uint64_t>(degree_max, (c->h_row_off[s + 1] - c->h_row_off[s]) + (uint64_t)columns);
-    }
+  SiteLdPass(const ngsld_site_ld_params *params, ngsld_site_ld_stats *out) : p(params), stats(out) {}
+
+  int validate(ngsld_ctx *c) override {
+    if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
+    if (const int rc = check_struct_sizes(c, p, "ngsld_site_ld_params", stats, "ngsld_site_ld_stats")) return rc;
+    if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "site_ld fields must be a non-empty mask of 1, 2, 4, 8");
+    if (std::isnan(p->max_kb_dist) || p->max_kb_dist < 0) return fail(c, NGSLD_ERR_INVALID, "site_ld max_kb_dist must be >= 0");
+    if (std::isnan(p->min_maf)) return fail(c, NGSLD_ERR_INVALID, "site_ld min_maf is NaN");
+    if (std::isnan(p->linked_min)) return fail(c, NGSLD_ERR_INVALID, "site_ld linked_min is NaN");
+    return NGSLD_OK;
   }
-  const uint64_t cols = std::min<uint64_t>(span + kTileRows, n);
-  uint64_t lds_budget = kLdsBudget;
-  if (const char *e = test_knob("SITE_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), kLdsBudget);
-  const bool use_lds = span > 0 && (uint64_t)words * cols * 8 <= lds_budget;
-  S.lds = use_lds ? 1 : 0;
-  const uint64_t chunk = record_chunk(test_knob("SITE_CHUNK_PAIRS"));
 
-  const uint64_t n_pairs = c->h_row_off[n];
-  S.pairs = n_pairs;
-  const size_t W = (size_t)words * n;
-  std::vector<unsigned long long> h_acc(W, 0);
-  if (n_pairs > 0) {
-    DevBuf<unsigned long long> d_acc, d_meta;
+  void clear(ngsld_ctx *c) override { c->clear_sites(); }
+
+  int prepare(ngsld_ctx *c, uint64_t) override {
+    const uint64_t n = c->n_sites;
+    if (const int rc = begin_pass(c, S)) return rc;
+    clear(c);
+    hipStream_t st = c->stream;
+    ns = field_list(p->fields, field);
+    words = 1u + 3u * (uint32_t)ns;
+
+    // ---- sites: the dist prefix sums, the maf filter on the printed maf ----
+    const double limit = p->max_kb_dist * 1000.0;
+    F.prepare(c, &p->min_maf);
+    if (const int rc = F.check_limit(c, "site_ld", limit)) return rc;
+
+    // ---- from the plan: how far a row reaches (the LDS window of a tile), how many rows a site can be in (the sums' bound) ----
+    uint64_t span = 0;
+    {
+      std::vector<int64_t> cover(n + 1, 0);  // +1 where a row's candidates begin, -1 where they end
+      for (uint64_t s = 0; s < n; ++s) {
+        if (c->h_row_off[s + 1] == c->h_row_off[s] || c->h_row_end[s] <= s + 1) continue;
+        span = std::max<uint64_t>(span, c->h_row_end[s] - s - 1);
+        ++cover[s + 1];
+        --cover[c->h_row_end[s]];
+      }
+      int64_t columns = 0;
+      for (uint64_t s = 0; s < n; ++s) {
+        columns += cover[s];
+        degree_max = std::max<uint64_t>(degree_max, (c->h_row_off[s + 1] - c->h_row_off[s]) + (uint64_t)columns);
+      }
+    }
+    cols = std::min<uint64_t>(span + kTileRows, n);
+    uint64_t lds_budget = kLdsBudget;
+    if (const char *e = test_knob("SITE_LDS_BYTES")) lds_budget = std::min<uint64_t>(std::strtoull(e, nullptr, 10), kLdsBudget);
+    use_lds = span > 0 && (uint64_t)words * cols * 8 <= lds_budget;
+    S.lds = use_lds ? 1 : 0;
+
+    const uint64_t n_pairs = c->h_row_off[n];
+    S.pairs = n_pairs;
+    W = (size_t)words * n;
+    h_acc.assign(W, 0);
+    if (n_pairs == 0) return NGSLD_OK;
     if (const int rc = F.upload(c)) return rc;
     HIP_TRY(c, d_acc.resize(W));
     HIP_TRY(c, d_meta.resize(2));
     HIP_TRY(c, hipMemsetAsync(d_acc.p, 0, W * sizeof(unsigned long long), st));
     HIP_TRY(c, hipMemsetAsync(d_meta.p, 0, 2 * sizeof(unsigned long long), st));
-    RecordPass R;
-    if (const int rc = R.open(c, chunk)) return rc;
-    SiteArgs A{};
     A.items = c->d_items.p;
     A.item_off = c->d_item_off.p;
-    A.rec = R.records();
     A.cum = F.d_cum.p;
     A.infc = F.d_infc.p;
     A.maf_ok = F.d_maf_ok.p;
@@ -248,7 +258,8 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
     A.acc = d_acc.p;
     A.meta = d_meta.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
-    const int rc = R.run(&S.pairs_ms, &S.site_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
+    client.kernel_ms = &S.site_ms;
+    client.launch = [this, c, st, max_blocks](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
       A.out_base = ch.out_base;
       A.r0 = ch.r0;
       A.r1 = ch.r1;
@@ -261,48 +272,78 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
         const unsigned blocks = std::min<unsigned>(blocks_for(n_items * 64), max_blocks);
         hipLaunchKernelGGL(site_kernel<false>, dim3(blocks), dim3(256), 0, st, A);
       }
-    }, [&](const RecordChunk &) -> int {
+    };
+    client.after = [this, c, st](const RecordChunk &) -> int {
       unsigned long long bad = 0;
       HIP_TRY(c, hipMemcpyAsync(&bad, d_meta.p, sizeof(bad), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
       return bad != 0 ? fail_value_range(c, "site_ld", bad) : NGSLD_OK;
-    });
-    if (rc != NGSLD_OK) return rc;
-    unsigned long long meta[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (A.track_max && sum_may_wrap(meta[1], degree_max))
-      return fail(c, NGSLD_ERR_UNSUPPORTED, "a site in up to " + std::to_string(degree_max) + " pairs with values too large to sum exactly");
+    };
+    return NGSLD_OK;
   }
 
-  // ---- the summaries: exact integer sums, one rounding for the mean ----
-  c->site_n.assign(h_acc.begin(), h_acc.begin() + n);
-  c->site_sum.resize((size_t)ns * n);
-  c->site_max.resize((size_t)ns * n);
-  c->site_linked.resize((size_t)ns * n);
-  c->site_mean.resize((size_t)ns * n);
-  uint64_t ends = 0;
-  for (uint64_t s = 0; s < n; ++s) {
-    const uint64_t rows = c->site_n[s];
-    ends += rows;
-    if (rows > 0) ++S.sites_with_pairs;
-    for (int v = 0; v < ns; ++v) {
-      const size_t k = (size_t)v * n + s;
-      // (no rows: nothing was added to the site's words)
-      const FieldSummary f = rows > 0 ? field_summary(h_acc.data(), n, v, s)
-                                      : FieldSummary{0, std::numeric_limits<int64_t>::min(), 0, std::numeric_limits<double>::quiet_NaN()};
-      c->site_sum[k] = f.sum;
-      c->site_max[k] = f.max;
-      c->site_linked[k] = f.linked;
-      c->site_mean[k] = f.mean;
+  void bind(ngsld_rec_std *records) override { A.rec = records; }
+
+  int finish(ngsld_ctx *c, const RecordPass::Shared &shared) override {
+    const uint64_t n = c->n_sites;
+    hipStream_t st = c->stream;
+    if (client.launch) {
+      S.pairs_ms = shared.pairs_ms;
+      S.chunks = shared.chunks;
+      unsigned long long meta[2] = {0, 0};
+      HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      if (A.track_max && sum_may_wrap(meta[1], degree_max))
+        return fail(c, NGSLD_ERR_UNSUPPORTED, "a site in up to " + std::to_string(degree_max) + " pairs with values too large to sum exactly");
     }
+
+    // ---- the summaries: exact integer sums, one rounding for the mean ----
+    c->site_n.assign(h_acc.begin(), h_acc.begin() + n);
+    c->site_sum.resize((size_t)ns * n);
+    c->site_max.resize((size_t)ns * n);
+    c->site_linked.resize((size_t)ns * n);
+    c->site_mean.resize((size_t)ns * n);
+    uint64_t ends = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t rows = c->site_n[s];
+      ends += rows;
+      if (rows > 0) ++S.sites_with_pairs;
+      for (int v = 0; v < ns; ++v) {
+        const size_t k = (size_t)v * n + s;
+        // (no rows: nothing was added to the site's words)
+        const FieldSummary f = rows > 0 ? field_summary(h_acc.data(), n, v, s)
+                                        : FieldSummary{0, std::numeric_limits<int64_t>::min(), 0, std::numeric_limits<double>::quiet_NaN()};
+        c->site_sum[k] = f.sum;
+        c->site_max[k] = f.max;
+        c->site_linked[k] = f.linked;
+        c->site_mean[k] = f.mean;
+      }
+    }
+    S.pairs_counted = ends / 2;
+    c->site_fields = p->fields;
+    S.total_ms = ms_since(t_all);
+    copy_stats(stats, S);
+    return NGSLD_OK;
   }
-  S.pairs_counted = ends / 2;
-  c->site_fields = p->fields;
-  S.total_ms = ms_since(t_all);
-  copy_stats(stats, S);
-  return NGSLD_OK;
+};
+
+}  // namespace
+
+namespace ngsld {
+namespace eng {
+std::unique_ptr<AnalysisPass> make_site_ld_pass(const ngsld_site_ld_params *p, ngsld_site_ld_stats *stats) {
+  return std::unique_ptr<AnalysisPass>(new SiteLdPass(p, stats));
+}
+}  // namespace eng
+}  // namespace ngsld
+
+extern "C" {
+
+int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_stats *stats) try {
+  if (c == nullptr) return NGSLD_ERR_INVALID;
+  SiteLdPass pass(p, stats);
+  return run_single(c, pass, record_chunk(test_knob("SITE_CHUNK_PAIRS")));
 } NGSLD_CATCH(c)
 
 int ngsld_site_ld_get(ngsld_ctx *c, int field, uint64_t *n, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean) {
