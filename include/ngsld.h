@@ -720,6 +720,49 @@ typedef struct {
 int ngsld_linked_pairs(ngsld_ctx *ctx, const ngsld_linked_params *params, const char *const *labels, ngsld_linked_fn sink,
                        void *user, ngsld_linked_stats *stats);
 
+/* ---- LD partners on the device (PARTNERS.md) --------------------------------------------------------------------------------
+ * For every site -- or every site of a query -- the k sites that tag it best, without the TSV: the pairs run again chunk by chunk
+ * into device records (every pair kernel, the exact-order replay included) and a kernel keeps, per site, the k largest of its
+ * partner rows.  An emitted pair (s1, s2) is a partner row iff it is a linked row of ngsld_linked_pairs under the same field,
+ * min_weight, abs_value, max_kb_dist and min_maf; it makes s2 a partner of s1 and s1 a partner of s2.  A site's partners are
+ * ranked by (printed value in micro-units descending -- |value| with abs_value --, partner index ascending): a total order, so
+ * every launch shape gives the same lists.  The rule and its deviations are in PARTNERS.md.  Both structs start with
+ * struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_partners_params) */
+  uint32_t k;                 /* partners kept per site, 1..64 */
+  int32_t field;              /* TSV column of the value: 4 r2_ExpG, 5 D, 6 D', 7 r2 (default) */
+  int32_t abs_value;          /* != 0 (default): |value| is compared and ranked; 0: the signed value */
+  double min_weight;          /* a row needs value >= min_weight (default 0.5; a value equal to it passes; -INFINITY allowed) */
+  double max_kb_dist;         /* finite: a row needs dist <= max_kb_dist * 1000; INFINITY (default): no condition on dist */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+} ngsld_partners_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_partners_stats) */
+  uint32_t reserved;          /* 0 */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t rows_counted;      /* partner rows (whether or not an end of theirs collects) */
+  uint64_t sites_with_partners;  /* collecting sites with a partner row */
+  uint64_t entries;           /* partners kept, over all sites */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, kernel_ms, total_ms;  /* pair kernels + replay, the partners kernel (kernel time), the whole call */
+} ngsld_partners_stats;
+
+/* The lists after ngsld_plan; the context keeps them until the next ngsld_partners, ngsld_plan or ngsld_set_*, and a call that
+ * fails leaves none.  query = n_sites bytes, a site collects partners iff its byte is not 0 (any site can be a partner); NULL:
+ * every site.  stats may be NULL.  A plan without pairs gives empty lists.  NGSLD_ERR_INVALID for a k outside 1..64, a field
+ * outside 4..7, a NaN min_weight or min_maf, a max_kb_dist that is NaN or below 0; NGSLD_ERR_UNSUPPORTED for a finite max_kb_dist
+ * with non-integer position gaps, and for a finite value of 2^31 micro-units or more (|x| >= 2147.483648, naming the pair) in a
+ * row that passes the maf and distance tests: nothing is wrapped or clamped. */
+int ngsld_partners(ngsld_ctx *ctx, const ngsld_partners_params *params, const uint8_t *query, ngsld_partners_stats *stats);
+/* The shape of the last ngsld_partners' lists (any pointer may be NULL); NGSLD_ERR_INVALID when there is none. */
+int ngsld_partners_info(ngsld_ctx *ctx, uint32_t *k, uint64_t *n_sites, uint32_t *field);
+/* The last ngsld_partners' lists, any pointer may be NULL: rows[n_sites] the site's partner rows before the cut to k,
+ * partner[n_sites * k] site indices in rank order (0xFFFFFFFF: none, from min(k, rows) on), value_micro[n_sites * k] the
+ * partner row's printed value * 10^6, signed as in the table unless abs_value (0 where there is no partner). */
+int ngsld_partners_get(ngsld_ctx *ctx, uint64_t *rows, uint32_t *partner, int64_t *value_micro);
+
 /* ---- LD scan on the device (SCAN.md) ----------------------------------------------------------------------------------------
  * The TSV this context's plan would print, scanned with a window centred on every site -- without the TSV: the pairs run again
  * chunk by chunk into device records (every pair kernel, the exact-order replay included) and a kernel adds every counted row
@@ -767,7 +810,7 @@ int ngsld_scan_get(ngsld_ctx *ctx, int field, uint32_t *win_first, uint32_t *win
  * ngsld_prune, ngsld_decay, ngsld_site_ld, ngsld_clusters, ngsld_grid and ngsld_scan each run every planned pair through the pair
  * kernels.  ngsld_analyze runs the pairs once, chunk of rows by chunk, and every listed analysis reads each chunk's records in
  * list order; the results are the single calls' bit for bit and are read through the single calls' getters (pruning's through
- * site_state).  ANALYZE.md has the rule.  ngsld_blocks and ngsld_linked_pairs stay calls of their own. */
+ * site_state).  ANALYZE.md has the rule.  ngsld_blocks, ngsld_linked_pairs and ngsld_partners stay calls of their own. */
 enum { NGSLD_AN_PRUNE = 1, NGSLD_AN_DECAY, NGSLD_AN_SITE_LD, NGSLD_AN_CLUSTERS, NGSLD_AN_GRID, NGSLD_AN_SCAN };
 
 typedef struct ngsld_analysis {

@@ -102,6 +102,7 @@ SYMBOLS = [
     "ngsld_linked_pairs",
     "ngsld_scan", "ngsld_scan_get",
     "ngsld_analyze",
+    "ngsld_partners", "ngsld_partners_info", "ngsld_partners_get",
 ]
 
 
@@ -199,6 +200,19 @@ class LinkedParams(C.Structure):
     """ngsld_linked_params (include/ngsld.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("min_weight", C.c_double), ("max_kb_dist", C.c_double),
                 ("min_maf", C.c_double), ("abs_value", C.c_int32), ("want", C.c_int32)]
+
+
+class PartnersParams(C.Structure):
+    """ngsld_partners_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("field", C.c_int32), ("abs_value", C.c_int32),
+                ("min_weight", C.c_double), ("max_kb_dist", C.c_double), ("min_maf", C.c_double)]
+
+
+class PartnersStats(C.Structure):
+    """ngsld_partners_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("rows_counted", C.c_uint64),
+                ("sites_with_partners", C.c_uint64), ("entries", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class ScanParams(C.Structure):
@@ -415,6 +429,10 @@ def lib() -> C.CDLL:
         if hasattr(L, "ngsld_scan"):
             L.ngsld_scan.argtypes = [vp, C.POINTER(ScanParams), C.POINTER(ScanStats)]
             L.ngsld_scan_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "ngsld_partners"):
+            L.ngsld_partners.argtypes = [vp, C.POINTER(PartnersParams), vp, C.POINTER(PartnersStats)]
+            L.ngsld_partners_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(C.c_uint32)]
+            L.ngsld_partners_get.argtypes = [vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1429,6 +1447,35 @@ class Engine:
         stats = {k: getattr(st, k) for k, _ in LinkedStats._fields_ if k not in ("struct_size", "reserved")}
         stats["batches"] = calls[0]
         return result, stats
+
+    def partners(self, k: int, field: int = 7, min_weight: float = 0.5, abs_value: bool = True, max_kb_dist: float = float("inf"),
+                 min_maf: float = 0.0, query=None) -> tuple[dict, dict]:
+        """Every site's top-k LD partners of the planned table on the device (ngsld_partners, PARTNERS.md): (result, stats).
+        result holds "rows" (uint64[n]: the site's partner rows before the cut to k), "partner" (int64[n, k]: site indices in
+        rank order, -1 for none), "value_micro" (int64[n, k]: the printed value * 10^6, |value| with abs_value) and "value"
+        (float64[n, k]: value_micro / 1e6, NaN for none).  query (optional): one entry per site, a site collects partners iff
+        its entry is not 0; any site can be a partner."""
+        p = PartnersParams(C.sizeof(PartnersParams), int(k), int(field), int(bool(abs_value)), float(min_weight),
+                           float(max_kb_dist), float(min_maf))
+        st = PartnersStats()
+        st.struct_size = C.sizeof(PartnersStats)
+        q = None
+        if query is not None:
+            q = np.ascontiguousarray(np.asarray(query) != 0, dtype=np.uint8)
+            if q.shape != (self.n_sites,):
+                raise ValueError(f"query must have one entry per site ({self.n_sites}): {q.shape}")
+        self._check(self._L.ngsld_partners(self._h, C.byref(p), None if q is None else q.ctypes.data, C.byref(st)))
+        kk, n, f = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        self._check(self._L.ngsld_partners_info(self._h, C.byref(kk), C.byref(n), C.byref(f)))
+        n, kk = int(n.value), int(kk.value)
+        rows = np.zeros(n, dtype=np.uint64)
+        partner = np.zeros((n, kk), dtype=np.uint32)
+        value_micro = np.zeros((n, kk), dtype=np.int64)
+        self._check(self._L.ngsld_partners_get(self._h, rows.ctypes.data, partner.ctypes.data, value_micro.ctypes.data))
+        none = partner == 0xFFFFFFFF
+        result = dict(rows=rows, partner=np.where(none, -1, partner.astype(np.int64)), value_micro=value_micro,
+                      value=np.where(none, np.nan, value_micro / 1e6))
+        return result, {k_: getattr(st, k_) for k_, _ in PartnersStats._fields_ if k_ not in ("struct_size", "reserved")}
 
     def blocks(self, labels: list[str], chr: str, start: int, end: int,
                ld=("r2", "Dp")) -> tuple[np.ndarray, dict, dict]:

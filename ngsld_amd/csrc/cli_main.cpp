@@ -31,6 +31,9 @@
 //   * --scan_out FILE --scan_half_window H (new) and the other --scan_* flags: a window of H bp to either side of every site --
 //     the rows inside its two flanks and across the site, Kelly's ZnS and Kim and Nielsen's omega -- summed on the device
 //     (ngsld_scan, SCAN.md); taken out of argv the same way, no TSV without --out;
+//   * --partners_out FILE --partners_k K (new) and the other --partners_* flags: for every site, or the sites --partners_sites
+//     names, the K sites that tag it best -- its rows at or above an LD floor ranked by value -- kept on the device
+//     (ngsld_partners, PARTNERS.md); taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -47,6 +50,7 @@
 #include <algorithm>
 #include <chrono>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/ngsld.h"
@@ -187,6 +191,16 @@ struct LinkedArgs {
   ngsld_linked_params p{};
 } linked;
 
+// ---- --partners_* (new): every site's top-K LD partners on the device ----
+struct PartnersArgs {
+  bool given = false;  // any --partners_* flag
+  const char *out = nullptr, *k = nullptr, *field = nullptr, *min_weight = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr,
+             *sites_file = nullptr;
+  bool is_signed = false;
+  std::vector<std::string> sites;  // the labels of --partners_sites
+  ngsld_partners_params p{};
+} partners;
+
 // ---- --scan_* (new): the LD scan on the device ----
 struct ScanArgs {
   bool given = false;  // any --scan_* flag
@@ -233,6 +247,25 @@ void one_device(const char *func, const Params &pars, const char *out_flag) {
   if (pars.devices.size() > 1) bad_value(func, out_flag, " runs on one device: it cannot be combined with --devices!");
 }
 
+// one label per line, plain or gzip-compressed (the script's IO::Zlib reads both); false: the file cannot be opened
+bool read_label_file(const char *path, std::vector<std::string> *labels) {
+  gzFile f = gzopen(path, "rb");
+  if (f == nullptr) return false;
+  std::string line;
+  char buf[4096];
+  while (gzgets(f, buf, sizeof(buf)) != nullptr) {
+    line += buf;
+    if (!line.empty() && line.back() == '\n') {
+      line.pop_back();
+      labels->push_back(line);
+      line.clear();
+    }
+  }
+  if (!line.empty()) labels->push_back(line);
+  gzclose(f);
+  return true;
+}
+
 void check_prune_args(const Params &pars) {
   PruneArgs *pa = &prune;
   if (pa->out == nullptr || *pa->out == 0) error(__FUNCTION__, "the --prune_* options need --prune_out FILE!");
@@ -260,22 +293,7 @@ void check_prune_args(const Params &pars) {
   number_arg(__FUNCTION__, "--prune_min_weight", pa->min_weight, &p.min_weight);
   if (pa->excl != nullptr && *pa->excl == 0) error(__FUNCTION__, "--prune_excl needs a file name!");
   one_device(__FUNCTION__, pars, "--prune_out");
-  if (pa->subset_file) {  // one label per line, plain or gzip-compressed (the script's IO::Zlib reads both)
-    gzFile f = gzopen(pa->subset_file, "rb");
-    if (f == nullptr) error(__FUNCTION__, "cannot open --prune_subset file!");
-    std::string line;
-    char buf[4096];
-    while (gzgets(f, buf, sizeof(buf)) != nullptr) {
-      line += buf;
-      if (!line.empty() && line.back() == '\n') {
-        line.pop_back();
-        pa->subset.push_back(line);
-        line.clear();
-      }
-    }
-    if (!line.empty()) pa->subset.push_back(line);
-    gzclose(f);
-  }
+  if (pa->subset_file && !read_label_file(pa->subset_file, &pa->subset)) error(__FUNCTION__, "cannot open --prune_subset file!");
 }
 
 // the statistics of --decay_ld, in TSV column order (bit k = column 4 + k)
@@ -451,6 +469,30 @@ void check_linked_args(const Params &pars) {
   dist_arg(__FUNCTION__, "--linked_max_kb_dist", la->max_kb_dist, &p.max_kb_dist);
   finite_arg(__FUNCTION__, "--linked_min_maf", la->min_maf, &p.min_maf);
   one_device(__FUNCTION__, pars, "--linked_out");
+}
+
+void check_partners_args(const Params &pars) {
+  PartnersArgs *pa = &partners;
+  if (pa->out == nullptr) error(__FUNCTION__, "the --partners_* options need --partners_out FILE!");
+  if (*pa->out == 0) error(__FUNCTION__, "--partners_out needs a file name!");
+  ngsld_partners_params &p = pa->p;
+  p.struct_size = sizeof(p);
+  p.field = 7;
+  p.min_weight = 0.5;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.abs_value = pa->is_signed ? 0 : 1;
+  if (pa->k == nullptr) error(__FUNCTION__, "--partners_out needs the partners kept per site: --partners_k INT!");
+  char *end = nullptr;
+  const long k = strtol(pa->k, &end, 10);
+  if (*pa->k == 0 || *end != 0 || k < 1 || k > 64) error(__FUNCTION__, "--partners_k must be an integer in [1,64]!");
+  p.k = (uint32_t)k;
+  column_arg(__FUNCTION__, "--partners_field", pa->field, &p.field);
+  number_arg(__FUNCTION__, "--partners_min_weight", pa->min_weight, &p.min_weight);
+  dist_arg(__FUNCTION__, "--partners_max_kb_dist", pa->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--partners_min_maf", pa->min_maf, &p.min_maf);
+  one_device(__FUNCTION__, pars, "--partners_out");
+  if (pa->sites_file && !read_label_file(pa->sites_file, &pa->sites)) error(__FUNCTION__, "cannot open --partners_sites file!");
 }
 
 void check_scan_args(const Params &pars) {
@@ -856,6 +898,56 @@ void run_linked(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
             (unsigned long)st.pairs, (unsigned long)st.text_bytes, (unsigned long)st.host_rows);
 }
 
+// every query site's partners, one line each: site, rank from 1, partner, the value as the table prints it
+void run_partners(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  PartnersArgs &pa = partners;
+  const uint64_t n = pars.n_sites;
+  std::vector<uint8_t> query;
+  if (pa.sites_file) {  // the labels up to their first TAB, as print_site names a site; without --pos the 1-based index
+    std::unordered_map<std::string, uint64_t> index;
+    for (uint64_t s = 0; s < n; ++s) {
+      if (pos) {
+        const char *lab = ngsld_host_label(pos, s);
+        index.emplace(std::string(lab, strcspn(lab, "\t")), s);
+      } else {
+        index.emplace(std::to_string(s + 1), s);
+      }
+    }
+    query.assign(n, 0);
+    for (const std::string &x : pa.sites) {
+      const auto it = index.find(x.substr(0, x.find('\t')));
+      if (it == index.end()) {
+        const std::string msg = "--partners_sites names a site that is not in the data: " + x;
+        error(__FUNCTION__, msg.c_str());
+      }
+      query[it->second] = 1;
+    }
+  }
+  ngsld_partners_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_partners(ctx, &pa.p, pa.sites_file ? query.data() : nullptr, &st) != NGSLD_OK) error("ngsld_partners", ngsld_last_error(ctx));
+  const uint32_t k = pa.p.k;
+  std::vector<uint64_t> rows(n);
+  std::vector<uint32_t> partner(n * k);
+  std::vector<int64_t> value(n * k);
+  if (ngsld_partners_get(ctx, rows.data(), partner.data(), value.data()) != NGSLD_OK) error("ngsld_partners_get", ngsld_last_error(ctx));
+  FILE *f = fopen(pa.out, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open LD partners output file!");
+  fprintf(f, "site\trank\tpartner\t%s\n", kDecayFields[pa.p.field - 4]);
+  for (uint64_t s = 0; s < n; ++s)
+    for (uint32_t j = 0; j < k && partner[s * k + j] != 0xffffffffu; ++j) {
+      print_site(f, pos, s);
+      fprintf(f, "\t%u\t", j + 1);
+      print_site(f, pos, partner[s * k + j]);
+      print_micro(f, value[s * k + j]);
+      fprintf(f, "\n");
+    }
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD partners output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD partners: %lu partners of %lu sites (up to %u each) from %lu partner rows of %lu pairs\n",
+            (unsigned long)st.entries, (unsigned long)st.sites_with_partners, k, (unsigned long)st.rows_counted, (unsigned long)st.pairs);
+}
+
 int write_blocks_text(void *user, const char *text, uint64_t len) {
   return fwrite(text, 1, len, static_cast<FILE *>(user)) == len ? 0 : 1;
 }
@@ -995,6 +1087,11 @@ const Family kFamilies[] = {
      {{"scan_out", &scan.out}, {"scan_half_window", &scan.half_window}, {"scan_ld", &scan.ld}, {"scan_max_kb_dist", &scan.max_kb_dist},
       {"scan_min_maf", &scan.min_maf}},
      nullptr, nullptr, &scan.given, check_scan_args, stage_scan, run_scan, write_scan, "LD scan"},
+    {"partners_",
+     {{"partners_out", &partners.out}, {"partners_k", &partners.k}, {"partners_field", &partners.field},
+      {"partners_min_weight", &partners.min_weight}, {"partners_max_kb_dist", &partners.max_kb_dist},
+      {"partners_min_maf", &partners.min_maf}, {"partners_sites", &partners.sites_file}},
+     "partners_signed", &partners.is_signed, &partners.given, check_partners_args, nullptr, run_partners, nullptr, "LD partners"},  // (a pass of the pair kernels of its own: lists that persist across its chunks)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1461,7 +1558,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
@@ -1592,7 +1689,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given && !grid.given && !linked.given &&  // (the clusters, the grid and the linked pairs need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given && !linked.given && !partners.given &&  // (the clusters, the grid, the linked pairs and the partners need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the

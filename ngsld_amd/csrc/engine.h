@@ -498,6 +498,19 @@ struct ngsld_ctx {
   } scan;
   void clear_scan() { scan = Scan(); }
 
+  // the lists of the last ngsld_partners (partners.hip), until the next ngsld_partners, ngsld_plan or ngsld_set_* (cleared with
+  // the block matrices): per site its partner rows, then [site][rank] the partner (0xFFFFFFFF: none) and its value in micro-units
+  uint32_t partners_k = 0, partners_field = 0;  // k 0: no result
+  std::vector<uint64_t> partners_rows;
+  std::vector<uint32_t> partners_partner;
+  std::vector<int64_t> partners_value;
+  void clear_partners() {
+    partners_k = partners_field = 0;
+    partners_rows.clear();
+    partners_partner.clear();
+    partners_value.clear();
+  }
+
   // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
   // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
   uint32_t blocks_fields = 0;
@@ -514,6 +527,7 @@ struct ngsld_ctx {
     clear_clusters();
     clear_grid();
     clear_scan();
+    clear_partners();
     blocks_fields = 0;
     blocks_members = 0;
     d_blocks_val.release();
