@@ -186,12 +186,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t *P, const uns
   }
 }
 
-// rank of TSV column `field` (4..7) among the chosen fields, -1 when it was not chosen
-int field_rank(uint32_t fields, int field) {
-  if (field < 4 || field > 7 || !((fields >> (field - 4)) & 1u)) return -1;
-  return __builtin_popcount(fields & ((1u << (field - 4)) - 1u));
-}
-
 }  // namespace
 
 extern "C" {
@@ -199,7 +193,7 @@ extern "C" {
 int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *labels, ngsld_blocks_stats *stats) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   const auto t_all = std::chrono::steady_clock::now();
-  c->clear_blocks();
+  c->res.blocks.clear();  // its own store alone: the other analyses' results stay
   if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
   if (const int rc = check_struct_sizes(c, p, "ngsld_blocks_params", stats, "ngsld_blocks_stats")) return rc;
   if (p->fields == 0 || p->fields > 15) return fail(c, NGSLD_ERR_INVALID, "blocks fields must be a non-empty mask of 1, 2, 4, 8");
@@ -256,9 +250,9 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, d_ord.resize(n_sites));
     HIP_TRY(c, d_count.resize(1));
     HIP_TRY(c, hipMemcpy(d_ord.p, ord.data(), n_sites * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, c->d_blocks_val.resize((size_t)ns * n * n));
-    HIP_TRY(c, c->d_blocks_present.resize((size_t)n * n));
-    HIP_TRY(c, hipMemsetAsync(c->d_blocks_present.p, 0, n * n, st));
+    HIP_TRY(c, c->res.blocks.d_val.resize((size_t)ns * n * n));
+    HIP_TRY(c, c->res.blocks.d_present.resize((size_t)n * n));
+    HIP_TRY(c, hipMemsetAsync(c->res.blocks.d_present.p, 0, n * n, st));
     HIP_TRY(c, hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
     // the member rows only: the rows of other sites are not run
     RecordPass R;
@@ -269,8 +263,8 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     A.n = n;
     A.ns = ns;
     for (int v = 0; v < 4; ++v) A.field[v] = field[v];
-    A.val = reinterpret_cast<unsigned long long *>(c->d_blocks_val.p);
-    A.present = c->d_blocks_present.p;
+    A.val = reinterpret_cast<unsigned long long *>(c->res.blocks.d_val.p);
+    A.present = c->res.blocks.d_present.p;
     A.in_region = d_count.p;
     const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 4;
     const int rc = R.run(&S.pairs_ms, &S.scatter_ms, &S.chunks, nullptr, [&](const RecordChunk &ch, const ngsld_item *items, uint64_t n_items) {
@@ -292,7 +286,7 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     HIP_TRY(c, ev.create());
     HIP_TRY(c, hipEventRecord(ev.a, st));
     hipLaunchKernelGGL(sites_kernel, dim3(blocks_for(n), (unsigned)((n + kSiteBand - 1) / kSiteBand)), dim3(256), 0, st,
-                       (const uint8_t *)c->d_blocks_present.p, n, d_mark.p);
+                       (const uint8_t *)c->res.blocks.d_present.p, n, d_mark.p);
     HIP_TRY(c, hipGetLastError());
     hipcub::CountingInputIterator<uint32_t> idx(0);
     size_t temp_bytes = 0;
@@ -311,31 +305,31 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
     if (m > 0) {
       std::vector<uint32_t> col(m);
       HIP_TRY(c, hipMemcpy(col.data(), d_col.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      HIP_TRY(c, c->d_blocks_col.resize(m));
-      HIP_TRY(c, hipMemcpy(c->d_blocks_col.p, col.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY(c, c->res.blocks.d_col.resize(m));
+      HIP_TRY(c, hipMemcpy(c->res.blocks.d_col.p, col.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
       std::vector<uint64_t> off(m + 1, 0);
       for (uint32_t k = 0; k < m; ++k) {
         const uint64_t s = mem[col[k]].site;
-        c->blocks_site.push_back(s);
-        c->blocks_label.push_back(label_pos(labels[s]).key);
-        off[k + 1] = off[k] + c->blocks_label.back().size();
+        c->res.blocks.site.push_back(s);
+        c->res.blocks.label.push_back(label_pos(labels[s]).key);
+        off[k + 1] = off[k] + c->res.blocks.label.back().size();
       }
       std::string blob;
       blob.reserve(off[m]);
-      for (const std::string &l : c->blocks_label) blob += l;
-      HIP_TRY(c, c->d_blocks_label.resize(std::max<size_t>(blob.size(), 1)));
-      HIP_TRY(c, c->d_blocks_label_off.resize(m + 1));
-      if (!blob.empty()) HIP_TRY(c, hipMemcpy(c->d_blocks_label.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(c->d_blocks_label_off.p, off.data(), (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+      for (const std::string &l : c->res.blocks.label) blob += l;
+      HIP_TRY(c, c->res.blocks.d_label.resize(std::max<size_t>(blob.size(), 1)));
+      HIP_TRY(c, c->res.blocks.d_label_off.resize(m + 1));
+      if (!blob.empty()) HIP_TRY(c, hipMemcpy(c->res.blocks.d_label.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(c->res.blocks.d_label_off.p, off.data(), (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
   }
-  if (c->blocks_site.empty()) {  // (no in-region pair: nothing to keep on the device)
-    c->d_blocks_val.release();
-    c->d_blocks_present.release();
+  if (c->res.blocks.site.empty()) {  // (no in-region pair: nothing to keep on the device)
+    c->res.blocks.d_val.release();
+    c->res.blocks.d_present.release();
   }
-  c->blocks_fields = p->fields;
-  c->blocks_members = n;
-  S.sites = c->blocks_site.size();
+  c->res.blocks.fields = p->fields;
+  c->res.blocks.members = n;
+  S.sites = c->res.blocks.site.size();
   S.cells_na = S.sites * S.sites - S.pairs_in_region;
   S.total_ms = ms_since(t_all);
   copy_stats(stats, S);
@@ -344,20 +338,20 @@ int ngsld_blocks(ngsld_ctx *c, const ngsld_blocks_params *p, const char *const *
 
 int ngsld_blocks_sites(ngsld_ctx *c, uint64_t cap, uint64_t *site, uint64_t *n_sites) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->blocks_fields == 0) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
-  const uint64_t m = c->blocks_site.size();
+  if (!c->res.blocks.valid()) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
+  const uint64_t m = c->res.blocks.site.size();
   if (n_sites) *n_sites = m;
   const uint64_t k = std::min<uint64_t>(cap, m);
-  if (k > 0 && site) std::memcpy(site, c->blocks_site.data(), k * sizeof(uint64_t));
+  if (k > 0 && site) std::memcpy(site, c->res.blocks.site.data(), k * sizeof(uint64_t));
   return NGSLD_OK;
 }
 
 int ngsld_blocks_matrix(ngsld_ctx *c, int field, double *values, uint8_t *present) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->blocks_fields == 0) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
-  const int v = field_rank(c->blocks_fields, field);
+  if (!c->res.blocks.valid()) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
+  const int v = field_rank(c->res.blocks.fields, field);
   if (v < 0) return fail(c, NGSLD_ERR_INVALID, "blocks field must be a TSV column 4..7 that ngsld_blocks was given");
-  const uint64_t m = c->blocks_site.size(), n = c->blocks_members;
+  const uint64_t m = c->res.blocks.site.size(), n = c->res.blocks.members;
   if (m == 0 || (values == nullptr && present == nullptr)) return NGSLD_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -367,9 +361,9 @@ int ngsld_blocks_matrix(ngsld_ctx *c, int field, double *values, uint8_t *presen
   HIP_TRY(c, d_present.resize(m * m));
   const unsigned max_blocks = (unsigned)std::max(1, c->n_cus) * 8;
   hipLaunchKernelGGL(gather_kernel, dim3(std::min<unsigned>(blocks_for(m * m), max_blocks)), dim3(256), 0, st,
-                     (const uint8_t *)c->d_blocks_present.p,
-                     reinterpret_cast<const unsigned long long *>(c->d_blocks_val.p) + (uint64_t)v * n * n, n,
-                     (const uint32_t *)c->d_blocks_col.p, m, d_val.p, d_present.p);
+                     (const uint8_t *)c->res.blocks.d_present.p,
+                     reinterpret_cast<const unsigned long long *>(c->res.blocks.d_val.p) + (uint64_t)v * n * n, n,
+                     (const uint32_t *)c->res.blocks.d_col.p, m, d_val.p, d_present.p);
   HIP_TRY(c, hipGetLastError());
   if (values) HIP_TRY(c, hipMemcpyAsync(values, d_val.p, m * m * sizeof(double), hipMemcpyDeviceToHost, st));
   if (present) HIP_TRY(c, hipMemcpyAsync(present, d_present.p, m * m, hipMemcpyDeviceToHost, st));
@@ -379,8 +373,8 @@ int ngsld_blocks_matrix(ngsld_ctx *c, int field, double *values, uint8_t *presen
 
 int ngsld_blocks_text(ngsld_ctx *c, int field, ngsld_text_fn sink, void *user, ngsld_blocks_stats *stats) try {
   if (c == nullptr || sink == nullptr) return NGSLD_ERR_INVALID;
-  if (c->blocks_fields == 0) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
-  const int v = field_rank(c->blocks_fields, field);
+  if (!c->res.blocks.valid()) return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks has not been called since the last plan or setting");
+  const int v = field_rank(c->res.blocks.fields, field);
   if (v < 0) return fail(c, NGSLD_ERR_INVALID, "blocks field must be a TSV column 4..7 that ngsld_blocks was given");
   if (stats != nullptr && stats->struct_size < sizeof(ngsld_blocks_stats))
     return fail(c, NGSLD_ERR_INVALID, "ngsld_blocks_stats: struct_size must be sizeof(ngsld_blocks_stats)");
@@ -394,10 +388,10 @@ int ngsld_blocks_text(ngsld_ctx *c, int field, ngsld_text_fn sink, void *user, n
     sink_ms += ms_since(t0);
     return rc == 0 ? NGSLD_OK : fail(c, NGSLD_ERR_SINK, "the blocks text sink returned non-zero");
   };
-  const uint64_t m = c->blocks_site.size(), n = c->blocks_members;
+  const uint64_t m = c->res.blocks.site.size(), n = c->res.blocks.members;
   {  // the label row: an empty first cell, then the sites
     std::string head;
-    for (const std::string &l : c->blocks_label) {
+    for (const std::string &l : c->res.blocks.label) {
       head += '\t';
       head += l;
     }
@@ -421,13 +415,13 @@ int ngsld_blocks_text(ngsld_ctx *c, int field, ngsld_text_fn sink, void *user, n
     const size_t scan_bytes = text_scan_temp_bytes(m);
     HIP_TRY(c, d_scan.resize(std::max<size_t>(scan_bytes, 1)));
     RowTextArgs A{};
-    A.present = c->d_blocks_present.p;
-    A.val = c->d_blocks_val.p + (uint64_t)v * n * n;
+    A.present = c->res.blocks.d_present.p;
+    A.val = c->res.blocks.d_val.p + (uint64_t)v * n * n;
     A.n = n;
-    A.col = c->d_blocks_col.p;
+    A.col = c->res.blocks.d_col.p;
     A.m = m;
-    A.labels = c->d_blocks_label.p;
-    A.label_off = c->d_blocks_label_off.p;
+    A.labels = c->res.blocks.d_label.p;
+    A.label_off = c->res.blocks.d_label_off.p;
     A.row0 = 0;
     A.n_rows = m;
     A.lens = d_lens.p;
@@ -484,14 +478,14 @@ int ngsld_blocks_text(ngsld_ctx *c, int field, ngsld_text_fn sink, void *user, n
         if (r == r1) break;
         if (h_col.empty()) {
           h_col.resize(m);
-          HIP_TRY(c, hipMemcpy(h_col.data(), c->d_blocks_col.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+          HIP_TRY(c, hipMemcpy(h_col.data(), c->res.blocks.d_col.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
           h_present.resize(n);
           h_val.resize(n);
         }
         const uint64_t a = h_col[r];
-        HIP_TRY(c, hipMemcpy(h_present.data(), c->d_blocks_present.p + a * n, n, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(h_val.data(), c->d_blocks_val.p + (uint64_t)v * n * n + a * n, n * sizeof(double), hipMemcpyDeviceToHost));
-        row = c->blocks_label[r];
+        HIP_TRY(c, hipMemcpy(h_present.data(), c->res.blocks.d_present.p + a * n, n, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(h_val.data(), c->res.blocks.d_val.p + (uint64_t)v * n * n + a * n, n * sizeof(double), hipMemcpyDeviceToHost));
+        row = c->res.blocks.label[r];
         for (uint64_t j = 0; j < m; ++j) {
           row += '\t';
           if (!h_present[h_col[j]]) {

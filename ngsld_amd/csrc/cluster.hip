@@ -173,7 +173,7 @@ struct ClustersPass final : AnalysisPass {
     return NGSLD_OK;
   }
 
-  void clear(ngsld_ctx *c) override { c->clear_clusters(); }
+  void clear(ngsld_ctx *c) override { c->res.clusters.clear(); }
 
   int prepare(ngsld_ctx *c, uint64_t) override {
     const uint64_t n = c->n_sites;
@@ -259,7 +259,7 @@ struct ClustersPass final : AnalysisPass {
 
     // ---- the clusters: a root is the smallest site of its component, so the roots come in id order ----
     const auto t_host = std::chrono::steady_clock::now();
-    ngsld_ctx::Clusters &K = c->clusters;
+    ClustersResult &K = c->res.clusters;
     K.id.assign(n, 0);
     for (uint64_t s = 0; s < n; ++s) {
       if (!node[s]) continue;
@@ -289,7 +289,7 @@ struct ClustersPass final : AnalysisPass {
     {  // the cluster of the most edges bounds every other's sums: the refusal names it
       const uint64_t most = nk ? *std::max_element(K.edges.begin(), K.edges.end()) : 0;
       if (track_max && track_sums(most >= (1ull << 25)) && sum_may_wrap(meta[1], most)) {
-        c->clear_clusters();
+        K.clear();
         return fail(c, NGSLD_ERR_UNSUPPORTED, "a cluster of " + std::to_string(most) + " edges with values too large to sum exactly");
       }
     }
@@ -310,7 +310,7 @@ struct ClustersPass final : AnalysisPass {
                               : div_nearest((unsigned __int128)edges, (unsigned __int128)size * (size - 1) / 2);
     }
     S.clusters = nk;
-    K.valid = true;
+    K.filled = true;
     S.finish_ms += ms_since(t_host);
     S.total_ms = ms_since(t_all);
     copy_stats(stats, S);
@@ -338,16 +338,16 @@ int ngsld_clusters(ngsld_ctx *c, const ngsld_clusters_params *p, ngsld_clusters_
 
 int ngsld_clusters_sites(ngsld_ctx *c, uint32_t *cluster) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (!c->clusters.valid) return fail(c, NGSLD_ERR_INVALID, "no ngsld_clusters result (it goes with the next ngsld_plan or ngsld_set_*)");
-  if (cluster && !c->clusters.id.empty()) std::memcpy(cluster, c->clusters.id.data(), c->clusters.id.size() * sizeof(uint32_t));
+  if (!c->res.clusters.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_clusters result (it goes with the next ngsld_plan or ngsld_set_*)");
+  if (cluster && !c->res.clusters.id.empty()) std::memcpy(cluster, c->res.clusters.id.data(), c->res.clusters.id.size() * sizeof(uint32_t));
   return NGSLD_OK;
 }
 
 int ngsld_clusters_table(ngsld_ctx *c, uint64_t min_size, uint64_t cap, uint32_t *id, uint32_t *size, uint32_t *first, uint32_t *last,
                          uint64_t *span, uint64_t *edges, int64_t *sum_micro, double *mean, double *density, uint64_t *n) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  const ngsld_ctx::Clusters &K = c->clusters;
-  if (!K.valid) return fail(c, NGSLD_ERR_INVALID, "no ngsld_clusters result (it goes with the next ngsld_plan or ngsld_set_*)");
+  const ClustersResult &K = c->res.clusters;
+  if (!K.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_clusters result (it goes with the next ngsld_plan or ngsld_set_*)");
   uint64_t rows = 0;
   for (size_t k = 0; k < K.size.size(); ++k) {
     if (K.size[k] < min_size) continue;

@@ -184,12 +184,7 @@ struct DecayPass final : AnalysisPass {
     return NGSLD_OK;
   }
 
-  void clear(ngsld_ctx *c) override {
-    c->decay_fields = 0;
-    c->decay_dist.clear();
-    c->decay_mean.clear();
-    c->decay_count.clear();
-  }
+  void clear(ngsld_ctx *c) override { c->res.decay.clear(); }
 
   int prepare(ngsld_ctx *c, uint64_t chunk_pairs) override {
     const uint64_t n = c->n_sites;
@@ -307,18 +302,18 @@ struct DecayPass final : AnalysisPass {
     const double B = p->bin_size;
     for (uint64_t k = 0; k < n_slots; ++k) {
       if (count[k] == 0) continue;
-      c->decay_dist.push_back(break_value(k, B));
-      c->decay_count.push_back(count[k]);
+      c->res.decay.dist.push_back(break_value(k, B));
+      c->res.decay.count.push_back(count[k]);
       S.pairs_counted += count[k];
       for (int v = 0; v < ns; ++v) {
         const __int128 s = (__int128)sum[v * n_slots + k];
         const unsigned __int128 a = (unsigned __int128)(s < 0 ? -s : s), b = (unsigned __int128)count[k] * 1000000u;
         const double m = div_nearest(a, b);
-        c->decay_mean.push_back(s < 0 ? -m : m);
+        c->res.decay.mean.push_back(s < 0 ? -m : m);
       }
     }
-    c->decay_fields = p->fields;
-    S.bins = c->decay_count.size();
+    c->res.decay.fields = p->fields;
+    S.bins = c->res.decay.count.size();
     S.total_ms = ms_since(t_all);
     copy_stats(stats, S);
     return NGSLD_OK;
@@ -345,13 +340,14 @@ int ngsld_decay(ngsld_ctx *c, const ngsld_decay_params *p, ngsld_decay_stats *st
 
 int ngsld_decay_bins(ngsld_ctx *c, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  const uint64_t nb = c->decay_count.size();
+  const DecayResult &D = c->res.decay;
+  const uint64_t nb = D.count.size();
   if (n_bins) *n_bins = nb;
   const uint64_t m = std::min<uint64_t>(cap, nb);
-  const int nf = __builtin_popcount(c->decay_fields);
-  if (m > 0 && dist) std::memcpy(dist, c->decay_dist.data(), m * sizeof(double));
-  if (m > 0 && count) std::memcpy(count, c->decay_count.data(), m * sizeof(uint64_t));
-  if (m > 0 && mean) std::memcpy(mean, c->decay_mean.data(), m * nf * sizeof(double));
+  const int nf = __builtin_popcount(D.fields);
+  if (m > 0 && dist) std::memcpy(dist, D.dist.data(), m * sizeof(double));
+  if (m > 0 && count) std::memcpy(count, D.count.data(), m * sizeof(uint64_t));
+  if (m > 0 && mean) std::memcpy(mean, D.mean.data(), m * nf * sizeof(double));
   return NGSLD_OK;
 }
 

@@ -249,6 +249,7 @@ using namespace ngsld;       // (an internal header: only the engine_*.hip units
 using namespace ngsld::eng;
 
 #include "exact_store.h"
+#include "results.h"
 
 // One pair a text batch leaves to the host's exact-order replay, written by the device right behind the batch's row lengths
 // (engine_replay.hip: flag_rows_to_host_kernel): with it the host replays the pair and overwrites the row's value columns in
@@ -441,108 +442,11 @@ struct ngsld_ctx {
   hipStream_t timed_stream = nullptr;
   uint64_t timed_pairs = 0;
 
-  // the bins of the last ngsld_decay (ngsld_decay_bins copies them out): lower break, rows, one mean per chosen field
-  uint32_t decay_fields = 0;
-  std::vector<double> decay_dist, decay_mean;  // decay_mean: [bin][field], fields in TSV column order
-  std::vector<uint64_t> decay_count;
-
-  // the per-site summaries of the last ngsld_site_ld (site_ld.hip), until the next ngsld_site_ld, ngsld_plan or ngsld_set_*
-  // (cleared with the block matrices): rows per site, then per chosen field [rank][site] the sum and the maximum in
-  // micro-units, the linked rows and the mean
-  uint32_t site_fields = 0;
-  std::vector<uint64_t> site_n, site_linked;
-  std::vector<int64_t> site_sum, site_max;
-  std::vector<double> site_mean;
-  void clear_sites() {
-    site_fields = 0;
-    site_n.clear();
-    site_linked.clear();
-    site_sum.clear();
-    site_max.clear();
-    site_mean.clear();
-  }
-
-  // the clusters of the last ngsld_clusters (cluster.hip), until the next ngsld_clusters, ngsld_plan or ngsld_set_* (cleared
-  // with the block matrices): every site's cluster id (0: not a node), then per cluster in id order its table row
-  struct Clusters {
-    bool valid = false;
-    std::vector<uint32_t> id, size, first, last;
-    std::vector<uint64_t> span, edges;
-    std::vector<int64_t> sum;
-    std::vector<double> mean, density;
-  } clusters;
-  void clear_clusters() { clusters = Clusters(); }
-
-  // the cells of the last ngsld_grid (grid.hip), until the next ngsld_grid, ngsld_plan or ngsld_set_* (cleared with the block
-  // matrices): the chromosomes in file order, then per cell with rows -- by chromosome, b1, b2 -- its chromosome, bins and rows,
-  // and per chosen field [rank][cell] the sum and the maximum in micro-units, the linked rows and the mean
-  struct Grid {
-    uint32_t fields = 0;
-    std::vector<std::string> chr_name;
-    std::vector<uint32_t> chr;
-    std::vector<uint64_t> b1, b2, n, linked;
-    std::vector<int64_t> sum, max;
-    std::vector<double> mean;
-  } grid;
-  void clear_grid() { grid = Grid(); }
-
-  // the windows of the last ngsld_scan (scan.hip), until the next ngsld_scan, ngsld_plan or ngsld_set_* (cleared with the block
-  // matrices): per site its window and the rows of the three classes, and per chosen field [rank][class LL, RR, LR][site] the
-  // sums in micro-units, then [rank][site] zns and omega
-  struct Scan {
-    uint32_t fields = 0;
-    std::vector<uint32_t> first, last;
-    std::vector<uint64_t> n;  // [class][site]
-    std::vector<int64_t> sum;
-    std::vector<double> zns, omega;
-  } scan;
-  void clear_scan() { scan = Scan(); }
-
-  // the lists of the last ngsld_partners (partners.hip), until the next ngsld_partners, ngsld_plan or ngsld_set_* (cleared with
-  // the block matrices): per site its partner rows, then [site][rank] the partner (0xFFFFFFFF: none) and its value in micro-units
-  uint32_t partners_k = 0, partners_field = 0;  // k 0: no result
-  std::vector<uint64_t> partners_rows;
-  std::vector<uint32_t> partners_partner;
-  std::vector<int64_t> partners_value;
-  void clear_partners() {
-    partners_k = partners_field = 0;
-    partners_rows.clear();
-    partners_partner.clear();
-    partners_value.clear();
-  }
-
-  // the matrices of the last ngsld_blocks (blocks.hip), until the next ngsld_blocks, ngsld_plan or ngsld_set_*: per chosen
-  // field a members x members matrix of the records' doubles, one presence byte per cell, the matrix sites
-  uint32_t blocks_fields = 0;
-  uint64_t blocks_members = 0;
-  DevBuf<double> d_blocks_val;                // [field rank][members][members], written only where present
-  DevBuf<uint8_t> d_blocks_present;           // [members][members]
-  DevBuf<uint32_t> d_blocks_col;              // [sites] member index of each matrix site, in matrix order
-  std::vector<uint64_t> blocks_site;          // [sites] site index of each matrix site
-  std::vector<std::string> blocks_label;      // [sites] its label up to the first TAB
-  DevBuf<char> d_blocks_label;                // ... back to back, for the text rows
-  DevBuf<uint64_t> d_blocks_label_off;        // [sites + 1]
-  void clear_blocks() {  // (every ngsld_plan and ngsld_set_* comes through here)
-    clear_sites();
-    clear_clusters();
-    clear_grid();
-    clear_scan();
-    clear_partners();
-    blocks_fields = 0;
-    blocks_members = 0;
-    d_blocks_val.release();
-    d_blocks_present.release();
-    d_blocks_col.release();
-    d_blocks_label.release();
-    d_blocks_label_off.release();
-    blocks_site.clear();
-    blocks_label.clear();
-  }
+  Results res;  // what the analyses leave until a getter copies it out, and the rule of what a new plan makes stale (results.h)
 };
 
 namespace ngsld {
 namespace eng {
-
 
 inline int fail(ngsld_ctx *c, int code, const std::string &msg) {
   if (c) c->err = msg;

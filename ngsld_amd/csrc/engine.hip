@@ -32,7 +32,7 @@ int set_geno_common(ngsld_ctx *c, const double *gl, const double *maf, uint64_t 
   c->store.reset();  // (the exact store of the device-side replay belongs to a matrix: its builder, if still at it, its buffers, its failure)
   c->have_geno = false;
   c->planned = false;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   c->text_mode = false;  // labels belong to a matrix
   c->replay_read = nullptr;  // and so does the replay source
   c->replay_user = nullptr;
@@ -373,7 +373,7 @@ int ngsld_set_pos_dist(ngsld_ctx *c, const double *pos_dist) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   if (!c->have_geno) return fail(c, NGSLD_ERR_INVALID, "set the genotype data before the positions");
   c->planned = false;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   if (pos_dist == nullptr)
     c->h_pos_dist.assign(c->n_sites, std::numeric_limits<double>::infinity());  // ngsLD.cpp:134
   else
@@ -418,7 +418,7 @@ int ngsld_describe_dispatch(uint64_t n_ind, int ignore_miss_data, char *buf, siz
 
 int ngsld_set_tuning(ngsld_ctx *c, uint32_t pairs_per_item, uint64_t batch_pairs) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   if (pairs_per_item) {
     c->pairs_per_item = pairs_per_item;
     c->planned = false;

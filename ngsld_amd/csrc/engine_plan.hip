@@ -136,7 +136,7 @@ int ngsld_plan(ngsld_ctx *c, const ngsld_params *p, uint64_t *n_pairs) try {
   const uint64_t n = c->n_sites;
   c->params = *p;
   c->planned = false;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   if (!(p->rnd_sample >= 0 && p->rnd_sample <= 1))  // parse_args.cpp:180-181 (0 is taken as "off" here)
     return fail(c, NGSLD_ERR_INVALID, "proportion of comparisons to sample must be in ]0,1]!");
   const bool sampling = p->rnd_sample > 0 && p->rnd_sample < 1;

@@ -615,7 +615,7 @@ static int set_replay_source(ngsld_ctx *c, const double *matrix, ngsld_read_site
   c->replay_read = read;
   c->replay_user = user;
   c->planned = false;  // a --min_maf tie is settled at plan time
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   return NGSLD_OK;
 }
 int ngsld_set_replay_source(ngsld_ctx *c, ngsld_read_sites_fn read, void *user) { return set_replay_source(c, nullptr, read, user); }
@@ -625,14 +625,14 @@ int ngsld_set_replay(ngsld_ctx *c, int enable) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   c->replay_on = enable != 0;
   c->planned = false;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   return NGSLD_OK;
 }
 
 int ngsld_set_exact_store(ngsld_ctx *c, int mode) {
   if (c == nullptr || mode < 0 || mode > 2) return NGSLD_ERR_INVALID;
   c->exact_mode = mode;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   return NGSLD_OK;
 }
 

@@ -167,7 +167,7 @@ int ngsld_set_text_output(ngsld_ctx *c, const char *const *labels, int enable) t
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // (a failure some earlier call already reported must not surface as a launch's "last error")
   c->text_mode = false;
-  c->clear_blocks();
+  c->res.invalidate_for_new_plan();
   if (!enable) return NGSLD_OK;
   c->have_labels = labels != nullptr;
   c->max_label = 6;

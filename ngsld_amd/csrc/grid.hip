@@ -248,7 +248,7 @@ struct GridPass final : AnalysisPass {
     return NGSLD_OK;
   }
 
-  void clear(ngsld_ctx *c) override { c->clear_grid(); }
+  void clear(ngsld_ctx *c) override { c->res.grid.clear(); }
 
   int prepare(ngsld_ctx *c, uint64_t) override {
     const uint64_t n = c->n_sites;
@@ -428,7 +428,7 @@ struct GridPass final : AnalysisPass {
     }
 
     // ---- the cells with rows, by chromosome, b1, b2 (the order of the words): exact integer sums, one rounding for the mean ----
-    ngsld_ctx::Grid &G = c->grid;
+    GridResult &G = c->res.grid;
     for (const Chr &ch : chrs) G.chr_name.push_back(ch.name);
     uint64_t n_cells = 0;
     for (uint64_t w = 0; w < cells; ++w) n_cells += h_acc[w] != 0;
@@ -494,8 +494,8 @@ int ngsld_grid(ngsld_ctx *c, const ngsld_grid_params *p, const char *const *labe
 
 int ngsld_grid_cells(ngsld_ctx *c, uint64_t cap, uint32_t *chr, uint64_t *bin1, uint64_t *bin2, uint64_t *n, uint64_t *n_cells) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->grid.fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
-  const ngsld_ctx::Grid &G = c->grid;
+  const GridResult &G = c->res.grid;
+  if (!G.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
   const uint64_t m = G.n.size(), k = std::min<uint64_t>(cap, m);
   if (n_cells) *n_cells = m;
   if (k == 0) return NGSLD_OK;
@@ -508,8 +508,8 @@ int ngsld_grid_cells(ngsld_ctx *c, uint64_t cap, uint32_t *chr, uint64_t *bin1, 
 
 int ngsld_grid_chromosomes(ngsld_ctx *c, uint64_t cap, const char **name, uint64_t *n_chr) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->grid.fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
-  const ngsld_ctx::Grid &G = c->grid;
+  const GridResult &G = c->res.grid;
+  if (!G.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
   if (n_chr) *n_chr = G.chr_name.size();
   if (name)
     for (uint64_t k = 0; k < std::min<uint64_t>(cap, G.chr_name.size()); ++k) name[k] = G.chr_name[k].c_str();
@@ -518,12 +518,11 @@ int ngsld_grid_chromosomes(ngsld_ctx *c, uint64_t cap, const char **name, uint64
 
 int ngsld_grid_get(ngsld_ctx *c, int field, uint64_t cap, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->grid.fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
-  const ngsld_ctx::Grid &G = c->grid;
-  if (field < 4 || field > 7 || !((G.fields >> (field - 4)) & 1u))
-    return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_grid (TSV column 4..7)");
-  const size_t before = (size_t)__builtin_popcount(G.fields & ((1u << (field - 4)) - 1u));
-  const size_t m = G.n.size(), at = before * m, k = (size_t)std::min<uint64_t>(cap, m);
+  const GridResult &G = c->res.grid;
+  if (!G.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)");
+  const int v = field_rank(G.fields, field);
+  if (v < 0) return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_grid (TSV column 4..7)");
+  const size_t m = G.n.size(), at = (size_t)v * m, k = (size_t)std::min<uint64_t>(cap, m);
   if (k == 0) return NGSLD_OK;
   if (sum_micro) std::memcpy(sum_micro, G.sum.data() + at, k * sizeof(int64_t));
   if (max_micro) std::memcpy(max_micro, G.max.data() + at, k * sizeof(int64_t));

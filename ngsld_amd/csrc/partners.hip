@@ -120,7 +120,7 @@ extern "C" {
 int ngsld_partners(ngsld_ctx *c, const ngsld_partners_params *p, const uint8_t *query, ngsld_partners_stats *stats) try {
   if (c == nullptr) return NGSLD_ERR_INVALID;
   const auto t_all = std::chrono::steady_clock::now();
-  c->clear_partners();
+  c->res.partners.clear();
   if (!c->planned) return fail(c, NGSLD_ERR_INVALID, "ngsld_plan has not been called");
   if (const int rc = check_struct_sizes(c, p, "ngsld_partners_params", stats, "ngsld_partners_stats")) return rc;
   if (p->k < 1 || p->k > kMaxK) return fail(c, NGSLD_ERR_INVALID, "partners k must be in 1..64");
@@ -233,11 +233,11 @@ int ngsld_partners(ngsld_ctx *c, const ngsld_partners_params *p, const uint8_t *
       ++S.entries;
     }
   }
-  c->partners_rows.assign(h_rows.begin(), h_rows.end());
-  c->partners_partner.swap(partner);
-  c->partners_value.swap(value);
-  c->partners_k = k;
-  c->partners_field = (uint32_t)p->field;
+  c->res.partners.rows.assign(h_rows.begin(), h_rows.end());
+  c->res.partners.partner.swap(partner);
+  c->res.partners.value.swap(value);
+  c->res.partners.k = k;
+  c->res.partners.field = (uint32_t)p->field;
   S.total_ms = ms_since(t_all);
   copy_stats(stats, S);
   return NGSLD_OK;
@@ -245,21 +245,21 @@ int ngsld_partners(ngsld_ctx *c, const ngsld_partners_params *p, const uint8_t *
 
 int ngsld_partners_info(ngsld_ctx *c, uint32_t *k, uint64_t *n_sites, uint32_t *field) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->partners_k == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_partners result (it goes with the next ngsld_plan or ngsld_set_*)");
-  if (k) *k = c->partners_k;
-  if (n_sites) *n_sites = c->partners_rows.size();
-  if (field) *field = c->partners_field;
+  if (!c->res.partners.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_partners result (it goes with the next ngsld_plan or ngsld_set_*)");
+  if (k) *k = c->res.partners.k;
+  if (n_sites) *n_sites = c->res.partners.rows.size();
+  if (field) *field = c->res.partners.field;
   return NGSLD_OK;
 }
 
 int ngsld_partners_get(ngsld_ctx *c, uint64_t *rows, uint32_t *partner, int64_t *value_micro) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->partners_k == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_partners result (it goes with the next ngsld_plan or ngsld_set_*)");
-  const size_t n = c->partners_rows.size(), m = n * c->partners_k;
+  if (!c->res.partners.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_partners result (it goes with the next ngsld_plan or ngsld_set_*)");
+  const size_t n = c->res.partners.rows.size(), m = n * c->res.partners.k;
   if (n == 0) return NGSLD_OK;
-  if (rows) std::memcpy(rows, c->partners_rows.data(), n * sizeof(uint64_t));
-  if (partner) std::memcpy(partner, c->partners_partner.data(), m * sizeof(uint32_t));
-  if (value_micro) std::memcpy(value_micro, c->partners_value.data(), m * sizeof(int64_t));
+  if (rows) std::memcpy(rows, c->res.partners.rows.data(), n * sizeof(uint64_t));
+  if (partner) std::memcpy(partner, c->res.partners.partner.data(), m * sizeof(uint32_t));
+  if (value_micro) std::memcpy(value_micro, c->res.partners.value.data(), m * sizeof(int64_t));
   return NGSLD_OK;
 }
 

@@ -192,7 +192,7 @@ struct ScanPass final : AnalysisPass {
     return NGSLD_OK;
   }
 
-  void clear(ngsld_ctx *c) override { c->clear_scan(); }
+  void clear(ngsld_ctx *c) override { c->res.scan.clear(); }
 
   int prepare(ngsld_ctx *c, uint64_t) override {
     const uint64_t n = c->n_sites;
@@ -325,7 +325,7 @@ struct ScanPass final : AnalysisPass {
     }
 
     // ---- per site: exact integer sums, one rounding each for zns and omega ----
-    ngsld_ctx::Scan &R = c->scan;
+    ScanResult &R = c->res.scan;
     R.first = std::move(win_a);
     R.last = std::move(win_b);
     R.n.resize(3 * n);
@@ -378,12 +378,11 @@ int ngsld_scan(ngsld_ctx *c, const ngsld_scan_params *p, ngsld_scan_stats *stats
 int ngsld_scan_get(ngsld_ctx *c, int field, uint32_t *win_first, uint32_t *win_last, uint64_t *n_ll, uint64_t *n_rr, uint64_t *n_lr,
                    int64_t *sum_ll, int64_t *sum_rr, int64_t *sum_lr, double *zns, double *omega) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  const ngsld_ctx::Scan &R = c->scan;
-  if (R.fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_scan result (it goes with the next ngsld_plan or ngsld_set_*)");
-  if (field < 4 || field > 7 || !((R.fields >> (field - 4)) & 1u))
-    return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_scan (TSV column 4..7)");
-  const size_t v = (size_t)__builtin_popcount(R.fields & ((1u << (field - 4)) - 1u));
-  const size_t m = R.first.size();
+  const ScanResult &R = c->res.scan;
+  if (!R.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_scan result (it goes with the next ngsld_plan or ngsld_set_*)");
+  const int rank = field_rank(R.fields, field);
+  if (rank < 0) return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_scan (TSV column 4..7)");
+  const size_t v = (size_t)rank, m = R.first.size();
   if (m == 0) return NGSLD_OK;
   if (win_first) std::memcpy(win_first, R.first.data(), m * sizeof(uint32_t));
   if (win_last) std::memcpy(win_last, R.last.data(), m * sizeof(uint32_t));

@@ -194,7 +194,7 @@ struct SiteLdPass final : AnalysisPass {
     return NGSLD_OK;
   }
 
-  void clear(ngsld_ctx *c) override { c->clear_sites(); }
+  void clear(ngsld_ctx *c) override { c->res.site_ld.clear(); }
 
   int prepare(ngsld_ctx *c, uint64_t) override {
     const uint64_t n = c->n_sites;
@@ -299,14 +299,14 @@ struct SiteLdPass final : AnalysisPass {
     }
 
     // ---- the summaries: exact integer sums, one rounding for the mean ----
-    c->site_n.assign(h_acc.begin(), h_acc.begin() + n);
-    c->site_sum.resize((size_t)ns * n);
-    c->site_max.resize((size_t)ns * n);
-    c->site_linked.resize((size_t)ns * n);
-    c->site_mean.resize((size_t)ns * n);
+    c->res.site_ld.n.assign(h_acc.begin(), h_acc.begin() + n);
+    c->res.site_ld.sum.resize((size_t)ns * n);
+    c->res.site_ld.max.resize((size_t)ns * n);
+    c->res.site_ld.linked.resize((size_t)ns * n);
+    c->res.site_ld.mean.resize((size_t)ns * n);
     uint64_t ends = 0;
     for (uint64_t s = 0; s < n; ++s) {
-      const uint64_t rows = c->site_n[s];
+      const uint64_t rows = c->res.site_ld.n[s];
       ends += rows;
       if (rows > 0) ++S.sites_with_pairs;
       for (int v = 0; v < ns; ++v) {
@@ -314,14 +314,14 @@ struct SiteLdPass final : AnalysisPass {
         // (no rows: nothing was added to the site's words)
         const FieldSummary f = rows > 0 ? field_summary(h_acc.data(), n, v, s)
                                         : FieldSummary{0, std::numeric_limits<int64_t>::min(), 0, std::numeric_limits<double>::quiet_NaN()};
-        c->site_sum[k] = f.sum;
-        c->site_max[k] = f.max;
-        c->site_linked[k] = f.linked;
-        c->site_mean[k] = f.mean;
+        c->res.site_ld.sum[k] = f.sum;
+        c->res.site_ld.max[k] = f.max;
+        c->res.site_ld.linked[k] = f.linked;
+        c->res.site_ld.mean[k] = f.mean;
       }
     }
     S.pairs_counted = ends / 2;
-    c->site_fields = p->fields;
+    c->res.site_ld.fields = p->fields;
     S.total_ms = ms_since(t_all);
     copy_stats(stats, S);
     return NGSLD_OK;
@@ -348,17 +348,17 @@ int ngsld_site_ld(ngsld_ctx *c, const ngsld_site_ld_params *p, ngsld_site_ld_sta
 
 int ngsld_site_ld_get(ngsld_ctx *c, int field, uint64_t *n, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean) {
   if (c == nullptr) return NGSLD_ERR_INVALID;
-  if (c->site_fields == 0) return fail(c, NGSLD_ERR_INVALID, "no ngsld_site_ld result (it goes with the next ngsld_plan or ngsld_set_*)");
-  if (field < 4 || field > 7 || !((c->site_fields >> (field - 4)) & 1u))
-    return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_site_ld (TSV column 4..7)");
-  const size_t ns_before = (size_t)__builtin_popcount(c->site_fields & ((1u << (field - 4)) - 1u));
-  const size_t m = c->site_n.size(), k = ns_before * m;
+  const SiteLdResult &R = c->res.site_ld;
+  if (!R.valid()) return fail(c, NGSLD_ERR_INVALID, "no ngsld_site_ld result (it goes with the next ngsld_plan or ngsld_set_*)");
+  const int v = field_rank(R.fields, field);
+  if (v < 0) return fail(c, NGSLD_ERR_INVALID, "not a field of the last ngsld_site_ld (TSV column 4..7)");
+  const size_t m = R.n.size(), k = (size_t)v * m;
   if (m == 0) return NGSLD_OK;
-  if (n) std::memcpy(n, c->site_n.data(), m * sizeof(uint64_t));
-  if (sum_micro) std::memcpy(sum_micro, c->site_sum.data() + k, m * sizeof(int64_t));
-  if (max_micro) std::memcpy(max_micro, c->site_max.data() + k, m * sizeof(int64_t));
-  if (linked) std::memcpy(linked, c->site_linked.data() + k, m * sizeof(uint64_t));
-  if (mean) std::memcpy(mean, c->site_mean.data() + k, m * sizeof(double));
+  if (n) std::memcpy(n, R.n.data(), m * sizeof(uint64_t));
+  if (sum_micro) std::memcpy(sum_micro, R.sum.data() + k, m * sizeof(int64_t));
+  if (max_micro) std::memcpy(max_micro, R.max.data() + k, m * sizeof(int64_t));
+  if (linked) std::memcpy(linked, R.linked.data() + k, m * sizeof(uint64_t));
+  if (mean) std::memcpy(mean, R.mean.data() + k, m * sizeof(double));
   return NGSLD_OK;
 }
 

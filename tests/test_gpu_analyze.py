@@ -462,3 +462,34 @@ def test_cli_one_invocation_writes_the_files_of_six(tmp_path):
     assert filecmp.cmp(tmp_path / "t2.tsv", tmp_path / "t0.tsv", shallow=False) and os.path.getsize(tmp_path / "t0.tsv") > 100_000
     for f in ("decay.tsv", "fit.tsv", "scan.tsv"):
         assert filecmp.cmp(tmp_path / f"two_{f}", tmp_path / f"one_{f}", shallow=False), f
+
+
+def test_cli_blocks_beside_a_bundle_leave_its_results_alone(tmp_path):
+    """--blocks_out beside two bundled families and no --out: ngsld_blocks runs between ngsld_analyze and the families' writers
+    (blocks come first in the families' order) and must not empty what the bundle left for them."""
+    inp = _input("plain")
+    n_sites, n_ind = inp.raw.shape[0], inp.raw.shape[1]
+    g, p = str(tmp_path / "g.bin"), str(tmp_path / "p.pos")
+    inp.raw.astype("<f8").tofile(g)
+    synth.write_pos(p, inp.chrs, inp.pos)
+    common = [capi.CLI_PATH, "--geno", g, "--n_ind", str(n_ind), "--n_sites", str(n_sites), "--max_kb_dist", "20", "--extend_out", "--pos", p]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("NGSLD_TEST_")}
+
+    def flags(tag):
+        return {"site": ["--site_out", f"{tag}_site.tsv", "--site_ld", "r2,D", "--site_signed"],
+                "grid": ["--grid_out", f"{tag}_grid.tsv", "--grid_bin_size", "2000", "--grid_ld", "r2,Dp"],
+                "blocks": ["--blocks_out", f"{tag}_B", "--blocks_chr", inp.chrs[40], "--blocks_start", str(int(inp.pos[40])),
+                           "--blocks_end", str(int(inp.pos[60]))]}
+
+    def run(*a):
+        return subprocess.run([*common, *a], capture_output=True, text=True, cwd=str(tmp_path), timeout=300, env=env)
+
+    r = run(*[x for fl in flags("all").values() for x in fl])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "==> analyses: 2 share one run of " in r.stderr and r.stdout == ""
+    for fl in flags("one").values():
+        r1 = run(*fl)
+        assert r1.returncode == 0, r1.stderr[-2000:]
+    for f in ("site.tsv", "grid.tsv", "B.r2.tsv", "B.Dp.tsv"):
+        assert os.path.getsize(tmp_path / f"one_{f}") > 100, f
+        assert filecmp.cmp(tmp_path / f"all_{f}", tmp_path / f"one_{f}", shallow=False), f

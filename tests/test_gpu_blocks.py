@@ -1,6 +1,7 @@
 """LD blocks on the device (ngsld_blocks, Engine.blocks / blocks_text, the binary's --blocks_* flags) against
 tests/blocks_ref.py -- the restatement of LD_blocks.sh -- applied to the same engine's own TSV (run_text) and, where it is
 built, to the reference program's table.  Every matrix file must be byte-identical."""
+import ctypes as C
 import os
 import subprocess
 
@@ -294,3 +295,139 @@ def test_blocks_of_the_reference_table(name, tmp_path):
     _, files, _ = blocks_ref.blocks(want_text, case.chrs[0], start, end, ld=("D",))
     assert "-0.000000" in files["D"] or "\t0.000000" in files["D"]
     print(f"{name}: {st['sites']} sites, {st['pairs_in_region']} pairs identical to the script on the reference table")
+
+
+# ---- the blocks beside the other analyses' results: every store has one owner (results.h) ----
+REFUSALS = {  # what each store's getters answer while it is empty
+    "site_ld": "no ngsld_site_ld result (it goes with the next ngsld_plan or ngsld_set_*)",
+    "clusters": "no ngsld_clusters result (it goes with the next ngsld_plan or ngsld_set_*)",
+    "grid": "no ngsld_grid result (it goes with the next ngsld_plan or ngsld_set_*)",
+    "scan": "no ngsld_scan result (it goes with the next ngsld_plan or ngsld_set_*)",
+    "partners": "no ngsld_partners result (it goes with the next ngsld_plan or ngsld_set_*)",
+    "blocks": "ngsld_blocks has not been called since the last plan or setting",
+}
+
+
+class Stores:
+    """The smallest context in which every analysis leaves a result: 60 sites on two chromosomes, 8 individuals, a window of
+    2 kb over gaps of up to 300 bp (every site has several pairs), the blocks' region a dozen sites of chr1.  fill() calls
+    each analysis once through its entry point; read(name) copies a store out through its getters alone."""
+    PLAN = dict(max_kb_dist=2, extend_out=False)
+
+    def __init__(self):
+        n, n_ind = 60, 8
+        self.raw = synth.make_gl_numpy(n, n_ind, 23, depth=4.0)
+        chrs, pos = synth.make_positions(n, 23, max_gap=300, n_chr=2)
+        self.labels = [f"{c}:{int(p)}" for c, p in zip(chrs, pos)]
+        self.region = ("chr1", int(pos[4]), int(pos[15]))
+        self.eng = capi.Engine(0)
+        try:
+            self.eng.set_geno_raw(self.raw)
+            self.eng.set_pos_dist(shard.pos_dist_from_positions(chrs, pos))
+            assert self.eng.plan(**self.PLAN) > 60 * 3
+            e = self.eng
+            self.jobs = dict(decay=e._decay_job(ld=ALL4, bin_size=100), site_ld=e._site_ld_job(ld=ALL4, linked_min=0.1),
+                             clusters=e._clusters_job(min_weight=0.1, min_size=1), grid=e._grid_job(self.labels, 1000, ld=ALL4),
+                             scan=e._scan_job(500, ld=ALL4))
+        except BaseException:
+            self.eng.close()
+            raise
+
+    def fill(self, names=("decay", "site_ld", "clusters", "grid", "scan", "partners", "blocks")):
+        for name in names:
+            if name == "partners":
+                self.eng.partners(3, min_weight=0.1)
+            elif name == "blocks":
+                assert self.eng.blocks(self.labels, *self.region, ld=ALL4)[2]["sites"] >= 10
+            else:
+                self.jobs[name].call()
+
+    def read(self, name) -> dict:
+        """The store's arrays as its getters return them now, by name; every getter must answer OK."""
+        L, h = self.eng._L, self.eng._h
+        if name == "partners":
+            k, n, f = C.c_uint32(), C.c_uint64(), C.c_uint32()
+            assert L.ngsld_partners_info(h, C.byref(k), C.byref(n), C.byref(f)) == capi.OK
+            out = dict(info=np.array([k.value, n.value, f.value]), rows=np.zeros(n.value, dtype=np.uint64),
+                       partner=np.zeros((n.value, k.value), dtype=np.uint32), value=np.zeros((n.value, k.value), dtype=np.int64))
+            assert L.ngsld_partners_get(h, out["rows"].ctypes.data, out["partner"].ctypes.data, out["value"].ctypes.data) == capi.OK
+            return out
+        if name == "blocks":
+            m = C.c_uint64()
+            assert L.ngsld_blocks_sites(h, 0, None, C.byref(m)) == capi.OK
+            m = m.value
+            out = dict(sites=np.zeros(m, dtype=np.uint64))
+            assert L.ngsld_blocks_sites(h, m, out["sites"].ctypes.data, None) == capi.OK
+            for k, f in enumerate(ALL4):
+                out[f], out[f"present_{f}"] = np.zeros((m, m)), np.zeros((m, m), dtype=np.uint8)
+                assert L.ngsld_blocks_matrix(h, 4 + k, out[f].ctypes.data, out[f"present_{f}"].ctypes.data) == capi.OK
+            return out
+        out = {}
+        for k, part in enumerate(self.jobs[name].read()[:-1]):  # (Engine's readers: the getters, each checked for OK)
+            out.update({f"{k}_{key}": v for key, v in part.items()} if isinstance(part, dict) else {str(k): part})
+        return out
+
+    def refusal(self, name) -> str:
+        """The named store's getters all answer ERR_INVALID; returns the message."""
+        L, h = self.eng._L, self.eng._h
+        n = C.c_uint64()
+        codes = {"site_ld": lambda: [L.ngsld_site_ld_get(h, 7, None, None, None, None, None)],
+                 "clusters": lambda: [L.ngsld_clusters_sites(h, None),
+                                      L.ngsld_clusters_table(h, 1, 0, None, None, None, None, None, None, None, None, None, C.byref(n))],
+                 "grid": lambda: [L.ngsld_grid_cells(h, 0, None, None, None, None, C.byref(n)), L.ngsld_grid_chromosomes(h, 0, None, C.byref(n)),
+                                  L.ngsld_grid_get(h, 7, 0, None, None, None, None)],
+                 "scan": lambda: [L.ngsld_scan_get(h, 7, None, None, None, None, None, None, None, None, None, None)],
+                 "partners": lambda: [L.ngsld_partners_info(h, None, None, None), L.ngsld_partners_get(h, None, None, None)],
+                 "blocks": lambda: [L.ngsld_blocks_sites(h, 0, None, C.byref(n)), L.ngsld_blocks_matrix(h, 7, None, None)]}[name]()
+        assert codes and all(c == capi.ERR_INVALID for c in codes), (name, codes)
+        return L.ngsld_last_error(h).decode()
+
+
+def _same_bits(got: dict, want: dict, where):
+    assert set(got) == set(want), where
+    for key, w in want.items():
+        g = got[key]
+        assert g.dtype == w.dtype and g.shape == w.shape, (where, key)
+        assert np.array_equal(np.frombuffer(g.tobytes(), np.uint8), np.frombuffer(w.tobytes(), np.uint8)), (where, key)
+
+
+def test_a_blocks_call_wipes_no_other_result():
+    s = Stores()
+    try:
+        others = ("site_ld", "clusters", "grid", "scan", "partners")
+        s.fill(others)
+        before = {name: s.read(name) for name in others}
+        # every store holds something: sites with rows, clusters, cells, windows with rows, partners
+        assert before["site_ld"]["0_n"].any() and len(before["clusters"]["1_id"]) > 0 and len(before["grid"]["0_n"]) > 0
+        assert before["scan"]["0_n_lr"].any() and before["scan"]["0_n_ll"].any() and before["partners"]["rows"].any()
+        s.fill(("blocks",))
+        for name in others:
+            _same_bits(s.read(name), before[name], name)
+        # ... and in the other direction: the matrices outlive the next ngsld_site_ld
+        blocks = s.read("blocks")
+        assert len(blocks["sites"]) >= 10 and blocks["present_r2"].any()
+        s.fill(("site_ld",))
+        _same_bits(s.read("blocks"), blocks, "blocks")
+        _same_bits(s.read("site_ld"), before["site_ld"], "site_ld again")
+    finally:
+        s.eng.close()
+
+
+@pytest.mark.parametrize("how", ["plan", "set_geno_raw"])
+def test_a_new_plan_or_matrix_empties_six_stores_and_keeps_the_decay_bins(how):
+    s = Stores()
+    try:
+        s.fill()
+        bins = s.read("decay")
+        assert len(bins["0_n"]) > 3
+        for name in REFUSALS:
+            s.read(name)  # (filled: every getter answers OK)
+        if how == "plan":
+            s.eng.plan(**s.PLAN)
+        else:
+            s.eng.set_geno_raw(s.raw)
+        for name, text in REFUSALS.items():
+            assert s.refusal(name) == text, name
+        _same_bits(s.read("decay"), bins, "decay")  # (indexed by distance, not by site: they stay until the next ngsld_decay)
+    finally:
+        s.eng.close()
