@@ -841,6 +841,57 @@ typedef struct ngsld_analyze_stats {
  * stats may be NULL. */
 int ngsld_analyze(ngsld_ctx *ctx, ngsld_analysis *list, uint32_t n, ngsld_analyze_stats *stats);
 
+/* ---- LD decay map on the device (DECAY_MAP.md) ------------------------------------------------------------------------------
+ * ngsld_decay's bins kept per group instead of pooled: a group is a chromosome (window == 0) or the window of `window` bp of a
+ * chromosome that holds the midpoint of the pair, w = (p1 + p2) / (2 * window) in integer division.  Chromosomes are the runs of
+ * sites between the non-finite gaps of pos_dist, as for ngsld_grid; a pair across chromosomes is never counted.  For each group
+ * the bins are what ngsld_decay gives for a TSV that holds only that group's rows: the same filters, right-closed bins and exact
+ * means (DECAY.md rules 1-6).  The fit is not run here: ngsld_host_decay_fit takes a group's bins.  It is a call of its own, not
+ * a kind of ngsld_analyze.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_decay_map_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (default) */
+  double bin_size;            /* B > 1, as ngsld_decay_params.bin_size */
+  double max_kb_dist;         /* a row needs dist < max_kb_dist * 1000 (INFINITY: no limit) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  uint64_t window;            /* 0: a group per chromosome; W in [1, 2^31): a group per window of W bp (the labels give the positions) */
+} ngsld_decay_map_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_decay_map_stats) */
+  uint32_t lds;               /* 1: a workgroup kept its home group's bins in LDS, 0: every add went to global memory */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows in some bin of some group */
+  uint64_t groups;            /* groups with a non-empty bin (what ngsld_decay_map_groups returns) */
+  uint64_t bins;              /* non-empty bins over all groups (what ngsld_decay_map_bins returns) */
+  uint64_t group_slots;       /* groups sized from the plan: chromosomes, or per chromosome the windows from its first to its last site */
+  uint64_t bin_slots;         /* bins per group sized from the plan */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  double pairs_ms, kernel_ms, total_ms;  /* pair kernels + replay, the map kernel (kernel time), the whole call */
+} ngsld_decay_map_stats;
+
+/* The map after ngsld_plan; the context keeps it until the next ngsld_decay_map, ngsld_plan or ngsld_set_*.  labels = n_sites C
+ * strings as ngsld_grid takes them, CHR ":" pos up to the first TAB.  window == 0: labels may be NULL (the groups are then named
+ * by their 1-based ordinal), otherwise a group is named by its first site's label up to the first ':'.  window > 0: NULL or
+ * "(null)" labels are NGSLD_ERR_INVALID; a position that is not plain decimal digits or is >= 2^62, and positions that decrease
+ * inside a chromosome, are NGSLD_ERR_UNSUPPORTED.  Also NGSLD_ERR_UNSUPPORTED: a value of 2^38 micro-units or more (naming the
+ * pair), sums that could pass 2^63 micro-units (max |value| x planned pairs), a finite max_kb_dist with non-integer position gaps,
+ * or accumulators of more than 1 GiB ((1 + fields) x group slots x bin slots x 8 B: a larger window or bin_size is needed;
+ * this stands in for ngsld_decay's limit of 2^22 bins).  Every refusal leaves the store empty and the context usable.  stats may be NULL. */
+int ngsld_decay_map(ngsld_ctx *ctx, const ngsld_decay_map_params *params, const char *const *labels, ngsld_decay_map_stats *stats);
+/* The chromosomes of the last ngsld_decay_map in file order: up to cap names into name[] (the context's strings: valid while the
+ * result is); *n_chr (may be NULL) receives their number. */
+int ngsld_decay_map_chromosomes(ngsld_ctx *ctx, uint64_t cap, const char **name, uint64_t *n_chr);
+/* The last ngsld_decay_map's groups with a non-empty bin, by chromosome (file order), then window: up to cap of them into chr[]
+ * (index into ngsld_decay_map_chromosomes' names), win_start[] (w * window; 0 per chromosome), first_bin[] and n_bins[] (the
+ * group's bins are entries first_bin .. first_bin + n_bins - 1 of ngsld_decay_map_bins).  Any pointer may be NULL; *n_groups (may
+ * be NULL) receives the number of groups. */
+int ngsld_decay_map_groups(ngsld_ctx *ctx, uint64_t cap, uint32_t *chr, uint64_t *win_start, uint64_t *first_bin, uint64_t *n_bins,
+                           uint64_t *n_groups);
+/* The non-empty bins of all groups back to back, each group's in increasing distance, as ngsld_decay_bins gives them: dist[],
+ * count[], mean[i * n_fields + f].  Any pointer may be NULL; *n_bins (may be NULL) receives the number of bins. */
+int ngsld_decay_map_bins(ngsld_ctx *ctx, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,7 @@ SYMBOLS = [
     "ngsld_scan", "ngsld_scan_get",
     "ngsld_analyze",
     "ngsld_partners", "ngsld_partners_info", "ngsld_partners_get",
+    "ngsld_decay_map", "ngsld_decay_map_chromosomes", "ngsld_decay_map_groups", "ngsld_decay_map_bins",
 ]
 
 
@@ -140,6 +141,19 @@ class DecayStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
                 ("bins", C.c_uint64), ("bin_slots", C.c_uint64), ("chunks", C.c_uint64), ("pairs_ms", C.c_double),
                 ("bin_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class DecayMapParams(C.Structure):
+    """ngsld_decay_map_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("bin_size", C.c_double), ("max_kb_dist", C.c_double),
+                ("min_maf", C.c_double), ("window", C.c_uint64)]
+
+
+class DecayMapStats(C.Structure):
+    """ngsld_decay_map_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("groups", C.c_uint64), ("bins", C.c_uint64), ("group_slots", C.c_uint64), ("bin_slots", C.c_uint64),
+                ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class BlocksParams(C.Structure):
@@ -433,6 +447,11 @@ def lib() -> C.CDLL:
             L.ngsld_partners.argtypes = [vp, C.POINTER(PartnersParams), vp, C.POINTER(PartnersStats)]
             L.ngsld_partners_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(C.c_uint32)]
             L.ngsld_partners_get.argtypes = [vp, vp, vp, vp]
+        if hasattr(L, "ngsld_decay_map"):
+            L.ngsld_decay_map.argtypes = [vp, C.POINTER(DecayMapParams), C.POINTER(C.c_char_p), C.POINTER(DecayMapStats)]
+            L.ngsld_decay_map_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
+            L.ngsld_decay_map_groups.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
+            L.ngsld_decay_map_bins.argtypes = [vp, u64, vp, vp, vp, C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -463,6 +482,13 @@ def decay_fit(dist, values, field: str = "r2", n_ind: float = 0, recomb_rate: fl
     if rc != OK:
         raise NgsldError(rc, f"ngsld_host_decay_fit refused the {field} fit")
     return {k: getattr(out, k) for k, _ in DecayFitResult._fields_}
+
+
+def decay_map_fit(groups: list[dict], field: str = "r2", n_ind: float = 0, recomb_rate: float = 1.0, min_bins: int = 3) -> list:
+    """decay_fit on each group of Engine.decay_map's list, in its order: the fit's dict, or None where the group has fewer than
+    min_bins bins (3: the parameters of the fit)."""
+    return [decay_fit(g["dist"], g[field], field, n_ind, recomb_rate) if len(g["dist"]) >= max(int(min_bins), 1) else None
+            for g in groups]
 
 
 def prune_graph(n_nodes: int, a, b, label, keep_heavy: bool = False, rank=None) -> tuple[np.ndarray, int]:
@@ -1214,6 +1240,49 @@ class Engine:
         for k, f in enumerate(names):
             bins[f] = mean[:nb, k].copy()
         return bins, {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}
+
+    def decay_map(self, labels: list[str] | None, window: int = 0, ld=("r2",), bin_size: float = 250,
+                  max_kb_dist: float = float("inf"), min_maf: float = 0.0) -> tuple[list, dict]:
+        """The LD decay map of the planned pairs on the device (ngsld_decay_map, DECAY_MAP.md): (groups, stats).  A group is a
+        chromosome (window 0; labels may be None, the groups are then named "1", "2", ...) or the window of `window` bp that
+        holds a pair's midpoint.  groups lists, in result order, {"chr", "win_start", "dist", "n", <one array per statistic>}:
+        the arrays are those Engine.decay returns for a table of that group's rows alone."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        names = [f for k, f in enumerate(DECAY_FIELDS) if (mask >> k) & 1]
+        arr = None if labels is None else (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels])
+        p = DecayMapParams(C.sizeof(DecayMapParams), mask, float(bin_size), float(max_kb_dist), float(min_maf), int(window))
+        st = DecayMapStats()
+        st.struct_size = C.sizeof(DecayMapStats)
+        self._check(self._L.ngsld_decay_map(self._h, C.byref(p), arr, C.byref(st)))
+        return self._decay_map_read(names), {k: getattr(st, k) for k, _ in DecayMapStats._fields_ if k != "struct_size"}
+
+    def _decay_map_read(self, names) -> list:
+        n_chr, ng, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.ngsld_decay_map_chromosomes(self._h, 0, None, C.byref(n_chr)))
+        chr_name = (C.c_char_p * max(int(n_chr.value), 1))()
+        self._check(self._L.ngsld_decay_map_chromosomes(self._h, int(n_chr.value), chr_name, None))
+        self._check(self._L.ngsld_decay_map_groups(self._h, 0, None, None, None, None, C.byref(ng)))
+        self._check(self._L.ngsld_decay_map_bins(self._h, 0, None, None, None, C.byref(nb)))
+        ng, nb = int(ng.value), int(nb.value)
+        idx = np.zeros(max(ng, 1), dtype=np.uint32)
+        win, first, length = (np.zeros(max(ng, 1), dtype=np.uint64) for _ in range(3))
+        dist, cnt = np.zeros(max(nb, 1)), np.zeros(max(nb, 1), dtype=np.uint64)
+        mean = np.zeros((max(nb, 1), len(names)))
+        self._check(self._L.ngsld_decay_map_groups(self._h, ng, idx.ctypes.data, win.ctypes.data, first.ctypes.data,
+                                                   length.ctypes.data, None))
+        self._check(self._L.ngsld_decay_map_bins(self._h, nb, dist.ctypes.data, cnt.ctypes.data, mean.ctypes.data, None))
+        groups = []
+        for g in range(ng):
+            a, b = int(first[g]), int(first[g] + length[g])
+            grp = {"chr": chr_name[int(idx[g])].decode(), "win_start": int(win[g]), "dist": dist[a:b].copy(), "n": cnt[a:b].copy()}
+            for k, f in enumerate(names):
+                grp[f] = mean[a:b, k].copy()
+            groups.append(grp)
+        return groups
 
     def site_ld(self, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0, linked_min: float = 0.5,
                 abs_value: bool = True) -> tuple[dict, dict]:

@@ -34,6 +34,9 @@
 //   * --partners_out FILE --partners_k K (new) and the other --partners_* flags: for every site, or the sites --partners_sites
 //     names, the K sites that tag it best -- its rows at or above an LD floor ranked by value -- kept on the device
 //     (ngsld_partners, PARTNERS.md); taken out of argv the same way, no TSV without --out;
+//   * --dmap_out FILE / --dmap_fit FILE (new) and the other --dmap_* flags: --decay_out's bins and --decay_fit's fit per
+//     chromosome, or with --dmap_window W per window of W bp, binned on the device (ngsld_decay_map, DECAY_MAP.md); taken out of
+//     argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -208,6 +211,16 @@ struct ScanArgs {
   ngsld_scan_params p{};
   ngsld_scan_stats st{};  // from the call to the writer
 } scan;
+
+// ---- --dmap_* (new): the LD decay map on the device ----
+struct DmapArgs {
+  bool given = false;  // any --dmap_* flag
+  const char *out = nullptr, *fit = nullptr, *window = nullptr, *ld = nullptr, *bin_size = nullptr, *max_kb_dist = nullptr,
+             *min_maf = nullptr, *n_ind = nullptr, *recomb_rate = nullptr, *fit_min_bins = nullptr;
+  ngsld_decay_map_params p{};
+  double n_ind_v = 0, recomb_rate_v = 1;
+  uint64_t fit_min_bins_v = 3;
+} dmap;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -520,6 +533,37 @@ void check_scan_args(const Params &pars) {
   one_device(__FUNCTION__, pars, "--scan_out");
 }
 
+// checked as the decay family is; --dmap_window (absent: a group per chromosome) needs the positions of --pos
+void check_dmap_args(const Params &pars) {
+  DmapArgs *ma = &dmap;
+  if (ma->out == nullptr && ma->fit == nullptr) error(__FUNCTION__, "the --dmap_* options need --dmap_out FILE or --dmap_fit FILE!");
+  if (ma->out != nullptr && *ma->out == 0) error(__FUNCTION__, "--dmap_out needs a file name!");
+  if (ma->fit != nullptr && *ma->fit == 0) error(__FUNCTION__, "--dmap_fit needs a file name!");
+  ngsld_decay_map_params &p = ma->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.bin_size = 250;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.window = 0;
+  ld_arg(__FUNCTION__, "--dmap_ld", ma->ld, &p.fields);
+  if (ma->bin_size && (!parse_double(ma->bin_size, &p.bin_size) || !(p.bin_size > 1) || std::isinf(p.bin_size)))
+    error(__FUNCTION__, "--dmap_bin_size must be a number > 1!");
+  dist_arg(__FUNCTION__, "--dmap_max_kb_dist", ma->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--dmap_min_maf", ma->min_maf, &p.min_maf);
+  finite_arg(__FUNCTION__, "--dmap_n_ind", ma->n_ind, &ma->n_ind_v);
+  if (ma->recomb_rate && (!parse_double(ma->recomb_rate, &ma->recomb_rate_v) || !(ma->recomb_rate_v > 0) || std::isinf(ma->recomb_rate_v)))
+    error(__FUNCTION__, "--dmap_recomb_rate must be a number > 0!");
+  if (ma->n_ind_v > 0 && (p.fields & (1u | 8u)) == 0) error(__FUNCTION__, "--dmap_n_ind is only used for the r2 and r2_ExpG fits!");
+  if (ma->n_ind_v > 0 && ma->fit != nullptr && (p.fields & 4u)) error(__FUNCTION__, "--dmap_n_ind cannot be combined with a Dp fit!");
+  if (ma->window && (!parse_position(ma->window, &p.window) || p.window < 1 || p.window >= (1ull << 31)))
+    error(__FUNCTION__, "--dmap_window must be an integer in [1, 2147483647]!");
+  if (ma->fit_min_bins && (!parse_position(ma->fit_min_bins, &ma->fit_min_bins_v) || ma->fit_min_bins_v < 3))
+    error(__FUNCTION__, "--dmap_fit_min_bins must be an integer >= 3 (the parameters of the fit)!");
+  if (ma->window != nullptr && pars.in_pos == nullptr) error(__FUNCTION__, "--dmap_window needs positions: it cannot run without --pos!");
+  one_device(__FUNCTION__, pars, "--dmap_out");
+}
+
 FILE *open_or_die(const char *path) {
   FILE *f = fopen(path, "w");
   if (f == nullptr) error(__FUNCTION__, "cannot open LD decay output file!");
@@ -600,6 +644,73 @@ void write_decay(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
   if (pars.verbose >= 1)
     fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)st.pairs_counted,
             (unsigned long)st.pairs);
+}
+
+// --dmap_out: chr, win_start, then --decay_out's own columns, one line per non-empty bin of every group; --dmap_fit: chr, win_start,
+// then --decay_fit's own columns, one line per group and fitted statistic (NA where the group has fewer bins than --dmap_fit_min_bins)
+void run_dmap(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  DmapArgs &ma = dmap;
+  std::vector<const char *> lab;
+  if (pos) {
+    lab.resize(pars.n_sites);
+    for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  }
+  ngsld_decay_map_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_decay_map(ctx, &ma.p, pos ? lab.data() : nullptr, &st) != NGSLD_OK) error("ngsld_decay_map", ngsld_last_error(ctx));
+  const std::vector<int> fields = fields_of(ma.p.fields);
+  const size_t nf = fields.size();
+  const uint64_t ng = st.groups, nb = st.bins;
+  uint64_t n_chr = 0;
+  if (ngsld_decay_map_chromosomes(ctx, 0, nullptr, &n_chr) != NGSLD_OK) error("ngsld_decay_map_chromosomes", ngsld_last_error(ctx));
+  std::vector<const char *> chr_name(n_chr);
+  if (ngsld_decay_map_chromosomes(ctx, n_chr, chr_name.data(), nullptr) != NGSLD_OK)
+    error("ngsld_decay_map_chromosomes", ngsld_last_error(ctx));
+  std::vector<uint32_t> chr(ng);
+  std::vector<uint64_t> win_start(ng), first(ng), len(ng), count(nb);
+  std::vector<double> dist(nb), mean(nb * nf);
+  if (ngsld_decay_map_groups(ctx, ng, chr.data(), win_start.data(), first.data(), len.data(), nullptr) != NGSLD_OK)
+    error("ngsld_decay_map_groups", ngsld_last_error(ctx));
+  if (ngsld_decay_map_bins(ctx, nb, dist.data(), count.data(), mean.data(), nullptr) != NGSLD_OK)
+    error("ngsld_decay_map_bins", ngsld_last_error(ctx));
+  if (ma.out) {
+    FILE *f = open_or_die(ma.out);
+    fprintf(f, "chr\twin_start\tdist\tn");
+    for (int k : fields) fprintf(f, "\t%s", kDecayFields[k]);
+    fprintf(f, "\n");
+    for (uint64_t g = 0; g < ng; ++g)
+      for (uint64_t i = first[g]; i < first[g] + len[g]; ++i) {
+        fprintf(f, "%s\t%lu\t%.15g\t%lu", chr_name[chr[g]], (unsigned long)win_start[g], dist[i], (unsigned long)count[i]);
+        for (size_t v = 0; v < nf; ++v) fprintf(f, "\t%.17g", mean[i * nf + v]);
+        fprintf(f, "\n");
+      }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay map output file!");
+  }
+  if (ma.fit) {
+    FILE *f = open_or_die(ma.fit);
+    fprintf(f, "chr\twin_start\tLD\tDecayRate\tLDmax\tLDmin\tSSE\tn_bins\n");
+    for (uint64_t g = 0; g < ng; ++g)
+      for (size_t v = 0; v < nf; ++v) {
+        if (fields[v] == 1) continue;  // (D has no model)
+        fprintf(f, "%s\t%lu\t%s", chr_name[chr[g]], (unsigned long)win_start[g], kDecayFields[fields[v]]);
+        std::vector<double> y(len[g]);
+        for (uint64_t i = 0; i < len[g]; ++i) y[i] = mean[(first[g] + i) * nf + v];
+        ngsld_decay_fit_result r{};
+        if (len[g] < ma.fit_min_bins_v) {
+          fprintf(f, "\tNA\tNA\tNA\tNA\t%lu\n", (unsigned long)len[g]);
+        } else if (ngsld_host_decay_fit(len[g], dist.data() + first[g], y.data(), 4 + fields[v], ma.n_ind_v, ma.recomb_rate_v, &r) != NGSLD_OK) {
+          const std::string msg = std::string("the ") + kDecayFields[fields[v]] + " fit is not defined on the bins of " + chr_name[chr[g]] +
+                                  ":" + std::to_string(win_start[g]) + " (Dp: a bin beyond 10^6 / recomb_rate bp)!";
+          error(__FUNCTION__, msg.c_str());
+        } else {
+          fprintf(f, "\t%.17g\t%.17g\t%.17g\t%.17g\t%lu\n", r.rate, r.ld_max, r.ld_min, r.sse, (unsigned long)r.n_bins);
+        }
+      }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay map fit file!");
+  }
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD decay map: %lu groups, %lu bins from %lu of %lu pairs\n", (unsigned long)ng, (unsigned long)nb,
+            (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
 }
 
 // a value in micro-units as exact six-decimal text
@@ -1039,7 +1150,7 @@ struct Family {
     const char *name;
     const char **dst;
   };
-  Valued valued[9];            // "--name value" or "--name=value"; a null name ends the list
+  Valued valued[12];           // "--name value" or "--name=value"; a null name ends the list
   const char *switch_name;     // a flag without a value (may be null) ...
   bool *switch_on;             // ... and where it goes
   bool *given;                 // any flag of the family
@@ -1092,6 +1203,11 @@ const Family kFamilies[] = {
       {"partners_min_weight", &partners.min_weight}, {"partners_max_kb_dist", &partners.max_kb_dist},
       {"partners_min_maf", &partners.min_maf}, {"partners_sites", &partners.sites_file}},
      "partners_signed", &partners.is_signed, &partners.given, check_partners_args, nullptr, run_partners, nullptr, "LD partners"},  // (a pass of the pair kernels of its own: lists that persist across its chunks)
+    {"dmap_",  // (not "decay_map_": a family is matched by its prefix, and decay_ would take those flags)
+     {{"dmap_out", &dmap.out}, {"dmap_fit", &dmap.fit}, {"dmap_window", &dmap.window}, {"dmap_ld", &dmap.ld},
+      {"dmap_bin_size", &dmap.bin_size}, {"dmap_max_kb_dist", &dmap.max_kb_dist}, {"dmap_min_maf", &dmap.min_maf},
+      {"dmap_n_ind", &dmap.n_ind}, {"dmap_recomb_rate", &dmap.recomb_rate}, {"dmap_fit_min_bins", &dmap.fit_min_bins}},
+     nullptr, nullptr, &dmap.given, check_dmap_args, nullptr, run_dmap, nullptr, "LD decay map"},  // (a pass of the pair kernels of its own: it is no kind of ngsld_analyze)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1558,7 +1674,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out / --dmap_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
@@ -1689,7 +1805,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given && !grid.given && !linked.given && !partners.given &&  // (the clusters, the grid, the linked pairs and the partners need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given && !linked.given && !partners.given && !dmap.given &&  // (the clusters, the grid, the linked pairs, the partners and the decay map need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the

@@ -12,6 +12,7 @@
 //   host     a chunk's int64 sums fold into 128-bit totals (with |q| < 2^38, a chunk of kRecordChunkPairs sums below 2^62); a
 //            bin's mean is the double nearest to sum / (10^6 * rows)
 #include "engine.h"
+#include "ld_decay_bins.h"
 #include "ld_prune.h"
 #include "record_pass.h"
 
@@ -39,19 +40,6 @@ struct BinArgs {
   unsigned long long *acc;    // [(1 + ns) * n_slots]: rows per bin, then the int64 sums of each field (two's complement)
   unsigned long long *meta;   // [0] (s1 << 32 | s2) + 1 of a value beyond 2^38 micro-units, [1] max |q|, [2] a bin beyond n_slots
 };
-
-// dist as the TSV prints it ("%.0f", read back): the exact binary value rounded half-to-even (exact for integer gaps)
-__host__ __device__ inline double printed_dist(double x) { return __builtin_rint(x); }
-
-// the right-closed bin (k*B, (k+1)*B] of d, with the breaks computed as R's seq(0, ., B) does (k * B); -1 for d <= 0
-__host__ __device__ inline long long bin_of(double d, double B) {
-  if (!(d > 0.0)) return -1;
-  long long k = (long long)__builtin_ceil(d / B) - 1;
-  if (k < 0) k = 0;
-  while (k > 0 && !(d > (double)k * B)) --k;
-  while (d > (double)(k + 1) * B) ++k;
-  return k;
-}
 
 template <bool kLds>
 __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
@@ -146,13 +134,6 @@ __global__ __launch_bounds__(256) void bin_kernel(BinArgs A) {
     for (uint32_t j = threadIdx.x; j < W; j += 256)
       if (lds[j] != 0) atomicAdd(A.acc + j, lds[j]);
   }
-}
-
-// R's as.character of a break (15 significant digits) read back
-double break_value(uint64_t k, double B) {
-  char buf[64];
-  std::snprintf(buf, sizeof(buf), "%.15g", (double)k * B);
-  return std::strtod(buf, nullptr);
 }
 
 // ngsld_decay in four parts (record_pass.h AnalysisPass)

@@ -18,7 +18,10 @@
 //   SITE_LDS_BYTES, SITE_CHUNK_PAIRS, CLUSTER_CHUNK_PAIRS, GRID_LDS_BYTES, GRID_CHUNK_PAIRS,
 //   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST, SCAN_CHUNK_PAIRS, SCAN_PLANT_DP,
 //   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT, ANALYZE_CHUNK_PAIRS,
-//   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS, PARTNERS_CHUNK_PAIRS, PARTNERS_PLANT_DP
+//   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS, PARTNERS_CHUNK_PAIRS, PARTNERS_PLANT_DP,
+//   DMAP_CHUNK_PAIRS, DMAP_LDS_BYTES
+// DMAP_CHUNK_PAIRS=n: ngsld_decay_map's chunks of rows hold about n pairs instead of 2^24 (decay_map.hip).  DMAP_LDS_BYTES=n: its
+// per-workgroup LDS budget for the home group's bins, at most 64 KiB; 0 sends every add to global memory.
 // PARTNERS_PLANT_DP=R:X: SCAN_PLANT_DP for ngsld_partners (partners.hip), whose refusal begins at 2^31 micro-units.
 // LINKED_FORCE_HOST=1: every chunk of ngsld_linked_pairs takes the host formatter, as BLOCKS_HOST_ROWS does for the block matrices.
 // SCAN_PLANT_DP=R:X: record R of the plan gets D' = X in ngsld_scan's record buffer before its kernel reads it (scan.hip) -- no input

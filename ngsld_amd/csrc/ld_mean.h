@@ -1,5 +1,5 @@
 // ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
-// (site_ld.hip), of ngsld_clusters' clusters (cluster.hip) and of ngsld_grid's cells (grid.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
+// (site_ld.hip), of ngsld_clusters' clusters (cluster.hip), of ngsld_grid's cells (grid.hip) and of ngsld_decay_map's bins (decay_map.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
 // compiles it alone.  ngsld_scan's omega (scan.hip) is a ratio of two such products, rounded once by ratio_nearest.
 #pragma once
 
@@ -31,6 +31,14 @@ inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
   sticky = sticky || (low & 1);
   if ((low & 2) && (sticky || (m & 1))) ++m;
   return std::ldexp((double)m, 2 - sh);
+}
+
+// div_nearest where a group map divides tens of thousands of means (decay_map.hip): operands below 2^53 are exact doubles, and
+// the IEEE quotient of two exact doubles is the double nearest to a / b, ties to even -- div_nearest's answer without its long
+// division (the build keeps -ffp-contract=off and no fast-math; tests/test_div_nearest_small.py holds the two to each other)
+inline double div_nearest_small(unsigned __int128 a, unsigned __int128 b) {
+  if ((a >> 53) == 0 && (b >> 53) == 0) return (double)(uint64_t)a / (double)(uint64_t)b;
+  return div_nearest(a, b);
 }
 
 // the double nearest to num / den (round half to even) for any num < 2^128 and 0 < den < 2^127, whatever the quotient: ngsld_scan's

@@ -1,5 +1,5 @@
 // results.h -- what the on-device analyses leave in the context until a getter copies it out: one struct per analysis with the test
-// its getters make (valid) and a clear of its own; Results holds the seven and the one rule of what a new plan makes stale.
+// its getters make (valid) and a clear of its own; Results holds the eight and the one rule of what a new plan makes stale.
 #pragma once  // (host code; engine.h includes it behind DevBuf)
 
 // rank of TSV column `field` (4..7) among the chosen fields (1 r2_ExpG, 2 D, 4 D', 8 r2), -1 when it was not chosen
@@ -86,11 +86,24 @@ struct BlocksResult {
   }
 };
 
+// ngsld_decay_map (decay_map.hip): the chromosomes in file order, then per group with a non-empty bin -- by chromosome, window --
+// its chromosome, win_start and the offset of its first bin (bin_off has one entry more: the end), then every group's non-empty
+// bins back to back as DecayResult holds them
+struct DecayMapResult {
+  uint32_t fields = 0;
+  std::vector<std::string> chr_name;
+  std::vector<uint32_t> chr;
+  std::vector<uint64_t> win_start, bin_off, count;
+  std::vector<double> dist, mean;
+  bool valid() const { return fields != 0; }  void clear() { *this = DecayMapResult(); }
+};
+
 // The lifetime rule, stated here alone.  An analysis clears its own store when it begins and touches no other.  ngsld_plan and every
-// ngsld_set_* call invalidate_for_new_plan: six stores hold values per site, region or cell of the plan that made them, which a new
+// ngsld_set_* call invalidate_for_new_plan: seven stores hold values per site, region, cell or group of the plan that made them, which a new
 // matrix, setting or plan makes stale.  The decay bins are indexed by distance, not by site: they stay until the next ngsld_decay.
 struct Results {
   DecayResult decay;  // (by distance: a new plan leaves it)
   BlocksResult blocks; SiteLdResult site_ld; ClustersResult clusters; GridResult grid; ScanResult scan; PartnersResult partners;
-  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); }
+  DecayMapResult decay_map;
+  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); decay_map.clear(); }
 };
