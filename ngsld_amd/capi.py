@@ -1236,10 +1236,15 @@ class Engine:
         got = C.c_uint64()
         self._check(self._L.ngsld_decay_bins(self._h, nb, dist.ctypes.data, cnt.ctypes.data, mean.ctypes.data, C.byref(got)))
         assert got.value == nb
-        bins = {"dist": dist[:nb], "n": cnt[:nb]}
+        return self._bin_columns(dist, cnt, mean, names, 0, nb), {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}
+
+    @staticmethod
+    def _bin_columns(dist, cnt, mean, names, a, b) -> dict:
+        """Bins a .. b - 1 of the arrays of ngsld_decay_bins / ngsld_decay_map_bins: one group's "dist", "n" and a mean per statistic."""
+        bins = {"dist": dist[a:b].copy(), "n": cnt[a:b].copy()}
         for k, f in enumerate(names):
-            bins[f] = mean[:nb, k].copy()
-        return bins, {k: getattr(st, k) for k, _ in DecayStats._fields_ if k != "struct_size"}
+            bins[f] = mean[a:b, k].copy()
+        return bins
 
     def decay_map(self, labels: list[str] | None, window: int = 0, ld=("r2",), bin_size: float = 250,
                   max_kb_dist: float = float("inf"), min_maf: float = 0.0) -> tuple[list, dict]:
@@ -1277,11 +1282,8 @@ class Engine:
         self._check(self._L.ngsld_decay_map_bins(self._h, nb, dist.ctypes.data, cnt.ctypes.data, mean.ctypes.data, None))
         groups = []
         for g in range(ng):
-            a, b = int(first[g]), int(first[g] + length[g])
-            grp = {"chr": chr_name[int(idx[g])].decode(), "win_start": int(win[g]), "dist": dist[a:b].copy(), "n": cnt[a:b].copy()}
-            for k, f in enumerate(names):
-                grp[f] = mean[a:b, k].copy()
-            groups.append(grp)
+            bins = self._bin_columns(dist, cnt, mean, names, int(first[g]), int(first[g] + length[g]))
+            groups.append({"chr": chr_name[int(idx[g])].decode(), "win_start": int(win[g]), **bins})
         return groups
 
     def site_ld(self, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0, linked_min: float = 0.5,

@@ -596,54 +596,65 @@ void run_decay(ngsld_ctx *ctx, const Params &, const ngsld_pos *) {
   if (ngsld_decay(ctx, &decay.p, &decay.st) != NGSLD_OK) error("ngsld_decay", ngsld_last_error(ctx));
 }
 
+// --decay_out's bin table, and --dmap_out's behind a prefix of "chr\twin_start\t": opened with its header, then one line per
+// non-empty bin: its lower break, rows, a mean per statistic (17 digits: the doubles themselves)
+FILE *open_bin_table(const char *path, const char *prefix, const std::vector<int> &fields) {
+  FILE *f = open_or_die(path);
+  fprintf(f, "%sdist\tn", prefix);
+  for (int k : fields) fprintf(f, "\t%s", kDecayFields[k]);
+  fprintf(f, "\n");
+  return f;
+}
+
+void write_bin_rows(FILE *f, const char *prefix, uint64_t nb, const double *dist, const uint64_t *count, const double *mean, size_t nf) {
+  for (uint64_t i = 0; i < nb; ++i) {
+    fprintf(f, "%s%.15g\t%lu", prefix, dist[i], (unsigned long)count[i]);
+    for (size_t v = 0; v < nf; ++v) fprintf(f, "\t%.17g", mean[i * nf + v]);
+    fprintf(f, "\n");
+  }
+}
+
+// --decay_fit's and --dmap_fit's line of statistic `field` (column v of the nb bins' means) behind its name; empty: no fit on these bins
+std::string fit_tail(uint64_t nb, const double *dist, const double *mean, size_t nf, size_t v, int field, double n_ind, double recomb_rate) {
+  std::vector<double> y(nb);
+  for (uint64_t i = 0; i < nb; ++i) y[i] = mean[i * nf + v];
+  ngsld_decay_fit_result r{};
+  if (ngsld_host_decay_fit(nb, dist, y.data(), 4 + field, n_ind, recomb_rate, &r) != NGSLD_OK) return std::string();
+  char buf[512];
+  std::snprintf(buf, sizeof(buf), "\t%.17g\t%.17g\t%.17g\t%.17g\t%lu\n", r.rate, r.ld_max, r.ld_min, r.sse, (unsigned long)r.n_bins);
+  return buf;
+}
+
 void write_decay(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
   DecayArgs &da = decay;
-  const ngsld_decay_stats &st = da.st;
   const std::vector<int> fields = fields_of(da.p.fields);
   const size_t nf = fields.size();
-  const uint64_t nb = st.bins;
+  const uint64_t nb = da.st.bins;
   std::vector<double> dist(nb), mean(nb * nf);
   std::vector<uint64_t> count(nb);
   if (ngsld_decay_bins(ctx, nb, dist.data(), count.data(), mean.data(), nullptr) != NGSLD_OK)
     error("ngsld_decay_bins", ngsld_last_error(ctx));
-  if (da.out) {  // one line per non-empty bin: its lower break, rows, a mean per statistic (17 digits: the doubles themselves)
-    FILE *f = open_or_die(da.out);
-    fprintf(f, "dist\tn");
-    for (int k : fields) fprintf(f, "\t%s", kDecayFields[k]);
-    fprintf(f, "\n");
-    for (uint64_t i = 0; i < nb; ++i) {
-      fprintf(f, "%.15g\t%lu", dist[i], (unsigned long)count[i]);
-      for (size_t v = 0; v < nf; ++v) fprintf(f, "\t%.17g", mean[i * nf + v]);
-      fprintf(f, "\n");
-    }
+  if (da.out) {
+    FILE *f = open_bin_table(da.out, "", fields);
+    write_bin_rows(f, "", nb, dist.data(), count.data(), mean.data(), nf);
     if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay output file!");
   }
-  if (da.fit) {  // one line per fitted statistic (D has no model)
+  if (da.fit) {  // one line per fitted statistic (D has no model); a fit that fails leaves no file
     if (nb == 0) error(__FUNCTION__, "no pair falls in a decay bin: nothing to fit!");
-    std::vector<std::string> lines;
+    std::string text = "LD\tDecayRate\tLDmax\tLDmin\tSSE\tn_bins\n";
     for (size_t v = 0; v < nf; ++v) {
       if (fields[v] == 1) continue;
-      std::vector<double> y(nb);
-      for (uint64_t i = 0; i < nb; ++i) y[i] = mean[i * nf + v];
-      ngsld_decay_fit_result r{};
-      if (ngsld_host_decay_fit(nb, dist.data(), y.data(), 4 + fields[v], da.n_ind_v, da.recomb_rate_v, &r) != NGSLD_OK) {
-        const std::string msg = std::string("the ") + kDecayFields[fields[v]] +
-                                " fit is not defined on these bins (Dp: a bin beyond 10^6 / recomb_rate bp)!";
-        error(__FUNCTION__, msg.c_str());
-      }
-      char buf[512];
-      std::snprintf(buf, sizeof(buf), "%s\t%.17g\t%.17g\t%.17g\t%.17g\t%lu\n", kDecayFields[fields[v]], r.rate, r.ld_max, r.ld_min,
-                    r.sse, (unsigned long)r.n_bins);
-      lines.push_back(buf);
+      const std::string name = kDecayFields[fields[v]], tail = fit_tail(nb, dist.data(), mean.data(), nf, v, fields[v], da.n_ind_v, da.recomb_rate_v);
+      if (tail.empty()) error(__FUNCTION__, ("the " + name + " fit is not defined on these bins (Dp: a bin beyond 10^6 / recomb_rate bp)!").c_str());
+      text += name + tail;
     }
     FILE *f = open_or_die(da.fit);
-    fprintf(f, "LD\tDecayRate\tLDmax\tLDmin\tSSE\tn_bins\n");
-    for (const std::string &l : lines) fputs(l.c_str(), f);
+    fputs(text.c_str(), f);
     if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay fit file!");
   }
   if (pars.verbose >= 1)
-    fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)st.pairs_counted,
-            (unsigned long)st.pairs);
+    fprintf(stderr, "==> LD decay: %lu bins from %lu of %lu pairs\n", (unsigned long)nb, (unsigned long)da.st.pairs_counted,
+            (unsigned long)da.st.pairs);
 }
 
 // --dmap_out: chr, win_start, then --decay_out's own columns, one line per non-empty bin of every group; --dmap_fit: chr, win_start,
@@ -673,17 +684,11 @@ void run_dmap(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
     error("ngsld_decay_map_groups", ngsld_last_error(ctx));
   if (ngsld_decay_map_bins(ctx, nb, dist.data(), count.data(), mean.data(), nullptr) != NGSLD_OK)
     error("ngsld_decay_map_bins", ngsld_last_error(ctx));
+  const auto prefix = [&](uint64_t g) { return std::string(chr_name[chr[g]]) + "\t" + std::to_string(win_start[g]) + "\t"; };
   if (ma.out) {
-    FILE *f = open_or_die(ma.out);
-    fprintf(f, "chr\twin_start\tdist\tn");
-    for (int k : fields) fprintf(f, "\t%s", kDecayFields[k]);
-    fprintf(f, "\n");
+    FILE *f = open_bin_table(ma.out, "chr\twin_start\t", fields);
     for (uint64_t g = 0; g < ng; ++g)
-      for (uint64_t i = first[g]; i < first[g] + len[g]; ++i) {
-        fprintf(f, "%s\t%lu\t%.15g\t%lu", chr_name[chr[g]], (unsigned long)win_start[g], dist[i], (unsigned long)count[i]);
-        for (size_t v = 0; v < nf; ++v) fprintf(f, "\t%.17g", mean[i * nf + v]);
-        fprintf(f, "\n");
-      }
+      write_bin_rows(f, prefix(g).c_str(), len[g], dist.data() + first[g], count.data() + first[g], mean.data() + first[g] * nf, nf);
     if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay map output file!");
   }
   if (ma.fit) {
@@ -692,19 +697,14 @@ void run_dmap(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
     for (uint64_t g = 0; g < ng; ++g)
       for (size_t v = 0; v < nf; ++v) {
         if (fields[v] == 1) continue;  // (D has no model)
-        fprintf(f, "%s\t%lu\t%s", chr_name[chr[g]], (unsigned long)win_start[g], kDecayFields[fields[v]]);
-        std::vector<double> y(len[g]);
-        for (uint64_t i = 0; i < len[g]; ++i) y[i] = mean[(first[g] + i) * nf + v];
-        ngsld_decay_fit_result r{};
-        if (len[g] < ma.fit_min_bins_v) {
-          fprintf(f, "\tNA\tNA\tNA\tNA\t%lu\n", (unsigned long)len[g]);
-        } else if (ngsld_host_decay_fit(len[g], dist.data() + first[g], y.data(), 4 + fields[v], ma.n_ind_v, ma.recomb_rate_v, &r) != NGSLD_OK) {
-          const std::string msg = std::string("the ") + kDecayFields[fields[v]] + " fit is not defined on the bins of " + chr_name[chr[g]] +
-                                  ":" + std::to_string(win_start[g]) + " (Dp: a bin beyond 10^6 / recomb_rate bp)!";
-          error(__FUNCTION__, msg.c_str());
-        } else {
-          fprintf(f, "\t%.17g\t%.17g\t%.17g\t%.17g\t%lu\n", r.rate, r.ld_max, r.ld_min, r.sse, (unsigned long)r.n_bins);
-        }
+        fprintf(f, "%s%s", prefix(g).c_str(), kDecayFields[fields[v]]);
+        const std::string tail = len[g] < ma.fit_min_bins_v
+                                     ? "\tNA\tNA\tNA\tNA\t" + std::to_string(len[g]) + "\n"
+                                     : fit_tail(len[g], dist.data() + first[g], mean.data() + first[g] * nf, nf, v, fields[v], ma.n_ind_v, ma.recomb_rate_v);
+        if (tail.empty())
+          error(__FUNCTION__, (std::string("the ") + kDecayFields[fields[v]] + " fit is not defined on the bins of " + chr_name[chr[g]] + ":" +
+                               std::to_string(win_start[g]) + " (Dp: a bin beyond 10^6 / recomb_rate bp)!").c_str());
+        fputs(tail.c_str(), f);
       }
     if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD decay map fit file!");
   }

@@ -1,11 +1,13 @@
-// ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's bins (decay.hip) and of ngsld_site_ld's sites
-// (site_ld.hip), of ngsld_clusters' clusters (cluster.hip), of ngsld_grid's cells (grid.hip) and of ngsld_decay_map's bins (decay_map.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
+// ld_mean.h -- the one rounding of an exact mean: the means of ngsld_decay's and ngsld_decay_map's bins (decay.hip, decay_map.hip:
+// append_bin_means) and of ngsld_site_ld's sites (site_ld.hip), of ngsld_clusters' clusters (cluster.hip) and of ngsld_grid's cells
+// (grid.hip) are sums of integer micro-units over counts, divided once.  Host code, no HIP: tests/test_div_nearest.py
 // compiles it alone.  ngsld_scan's omega (scan.hip) is a ratio of two such products, rounded once by ratio_nearest.
 #pragma once
 
 #include <stdint.h>
 
 #include <cmath>
+#include <vector>
 
 namespace ngsld {
 namespace eng {
@@ -33,7 +35,7 @@ inline double div_nearest(unsigned __int128 a, unsigned __int128 b) {
   return std::ldexp((double)m, 2 - sh);
 }
 
-// div_nearest where a group map divides tens of thousands of means (decay_map.hip): operands below 2^53 are exact doubles, and
+// div_nearest where a group map divides tens of thousands of means (append_bin_means): operands below 2^53 are exact doubles, and
 // the IEEE quotient of two exact doubles is the double nearest to a / b, ties to even -- div_nearest's answer without its long
 // division (the build keeps -ffp-contract=off and no fast-math; tests/test_div_nearest_small.py holds the two to each other)
 inline double div_nearest_small(unsigned __int128 a, unsigned __int128 b) {
@@ -83,6 +85,27 @@ inline double ratio_nearest(unsigned __int128 num, unsigned __int128 den) {
 inline double mean_nearest(uint64_t sum, uint64_t rows) {
   if (sum < (1ull << 53) && rows < (1ull << 33)) return (double)sum / (double)(rows * 1000000u);
   return div_nearest((unsigned __int128)sum, (unsigned __int128)rows * 1000000u);
+}
+
+// One group's non-empty bins of LD decay, appended to dist, count and mean ([bin][field]): bin k holds rows[k] rows, sum(v, k) is the
+// signed sum of their micro-units of field v (an __int128 holds decay's totals over every chunk), lower(k) the bin's label.  A mean
+// is the double nearest to sum / (10^6 * rows) (100 groups x 400 bins x 4 statistics: 160,000 of them).  Returns the rows appended.
+template <class Sum, class Lower>
+uint64_t append_bin_means(uint64_t n_bins, const uint64_t *rows, int ns, Sum sum, Lower lower, std::vector<double> &dist,
+                          std::vector<uint64_t> &count, std::vector<double> &mean) {
+  uint64_t appended = 0;
+  for (uint64_t k = 0; k < n_bins; ++k) {
+    if (rows[k] == 0) continue;
+    dist.push_back(lower(k));
+    count.push_back(rows[k]);
+    appended += rows[k];
+    for (int v = 0; v < ns; ++v) {
+      const __int128 s = sum(v, k);
+      const double m = div_nearest_small((unsigned __int128)(s < 0 ? -s : s), (unsigned __int128)rows[k] * 1000000u);
+      mean.push_back(s < 0 ? -m : m);
+    }
+  }
+  return appended;
 }
 
 }  // namespace eng

@@ -3,7 +3,8 @@
 // and ngsld_scan (scan.hip) read the records of rows chunk
 // by chunk and run a kernel of their own over each chunk's items (ld_records.h).  What they share on the host is here, once: the
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
-// linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ.
+// linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ -- but for
+// ngsld_decay and ngsld_decay_map (decay_map.hip), whose filter is one and which run one kernel (ld_decay_bins.h).
 // (ngsld_scan uses the site filter, the chunk loop, the two refusals and the guard of the sums.)
 // The chunk loop takes a list of passes: the pairs of a chunk run once and every pass of the list reads them (ngsld_analyze,
 // analyze.hip); the six passes it can list are AnalysisPass objects, and their single calls are a list of one.
