@@ -892,6 +892,60 @@ int ngsld_decay_map_groups(ngsld_ctx *ctx, uint64_t cap, uint32_t *chr, uint64_t
  * count[], mean[i * n_fields + f].  Any pointer may be NULL; *n_bins (may be NULL) receives the number of bins. */
 int ngsld_decay_map_bins(ngsld_ctx *ctx, uint64_t cap, double *dist, uint64_t *count, double *mean, uint64_t *n_bins);
 
+/* ---- LD across chromosomes on the device (CROSS.md) -------------------------------------------------------------------------
+ * The whole-genome form of ngsld_grid: the rows of the TSV this context's plan would print, those across two chromosomes (dist
+ * not finite) included, binned by the chromosome and window of both sites -- without the TSV.  Chromosomes are the runs of sites
+ * between the non-finite gaps of pos_dist; a site's bin is p / bin_size in integer division (bin_size == 0: one bin per
+ * chromosome), the bins numbered consecutively over the chromosomes.  A row (s1 < s2) counts iff both printed maf >= min_maf,
+ * every chosen field is finite, and either the sites lie on two chromosomes or within != 0 and dist (as printed) >=
+ * min_kb_dist * 1000.  It belongs to the cell (chr, bin of s1; chr, bin of s2).  Per cell: what ngsld_grid keeps per cell, as
+ * exact integers in micro-units, and the mean as the double nearest to the exact mean.  It is a call of its own, not a kind of
+ * ngsld_analyze.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_cross_ld_params) */
+  uint32_t fields;            /* mask as ngsld_decay_params.fields: 1 r2_ExpG, 2 D, 4 D', 8 r2 (default) */
+  uint64_t bin_size;          /* B: 0 = one bin per chromosome; else the window in bp, 1 <= B < 2^31 (the labels give the positions) */
+  double min_maf;             /* a row needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  double linked_min;          /* a row is linked in a field iff its value >= linked_min (default 0.5) */
+  double min_kb_dist;         /* a row inside one chromosome needs dist >= min_kb_dist * 1000 (default 0) */
+  int32_t abs_value;          /* != 0 (default): |value|; 0: the signed value */
+  int32_t within;             /* != 0 (default): rows inside one chromosome count too; 0: only rows across two chromosomes */
+} ngsld_cross_ld_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_cross_ld_stats) */
+  uint32_t lds;               /* 0: every add that leaves a wavefront goes to global memory (there is no LDS form) */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t pairs_counted;     /* rows that count: the sum of n over the cells */
+  uint64_t pairs_cross;       /* ... of them across two chromosomes */
+  uint64_t cells;             /* cells with rows (what ngsld_cross_ld_cells returns) */
+  uint64_t bins;              /* bins between the first and the last site of every chromosome; the accumulators hold bins * (bins + 1) / 2 cells */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  uint64_t span_items;        /* M: consecutive work items a wavefront carries its current cell over */
+  double pairs_ms, cross_ms, total_ms;  /* pair kernels + replay, the cross kernel (kernel time), the whole call */
+} ngsld_cross_ld_stats;
+
+/* The cells after ngsld_plan; the context keeps them until the next ngsld_cross_ld, ngsld_plan or ngsld_set_*.  labels = n_sites
+ * C strings as ngsld_grid takes them, CHR ":" pos up to the first TAB.  bin_size == 0: labels may be NULL (the chromosomes are
+ * then named by their 1-based ordinal); bin_size > 0: NULL or "(null)" labels are NGSLD_ERR_INVALID.  NGSLD_ERR_INVALID too
+ * where pos_dist holds no finite gap at all.  NGSLD_ERR_UNSUPPORTED as for ngsld_grid: labels that disagree with pos_dist, a
+ * chromosome name that begins two runs, positions that are not plain decimal digits or that decrease, a value of 2^38
+ * micro-units or more (naming the pair), a cell whose sum could pass 2^63 micro-units, min_kb_dist > 0 with non-integer position
+ * gaps, or accumulators of more than 2 GiB ((1 + 3 x fields) x bins x (bins + 1) / 2 x 8 B: a larger bin_size is needed).  Every
+ * refusal leaves the store empty and the context usable.  stats may be NULL. */
+int ngsld_cross_ld(ngsld_ctx *ctx, const ngsld_cross_ld_params *params, const char *const *labels, ngsld_cross_ld_stats *stats);
+/* The last ngsld_cross_ld's cells with rows, ordered by the consecutive bin of the first site, then of the second: up to cap of
+ * them into chr1[] and chr2[] (indices into ngsld_cross_ld_chromosomes' names), bin1[] and bin2[] (the bins b = p / bin_size; 0
+ * with bin_size 0) and n[] (rows).  Any pointer may be NULL; *n_cells (may be NULL) receives the number of cells. */
+int ngsld_cross_ld_cells(ngsld_ctx *ctx, uint64_t cap, uint32_t *chr1, uint64_t *bin1, uint32_t *chr2, uint64_t *bin2, uint64_t *n,
+                         uint64_t *n_cells);
+/* The chromosomes of the last ngsld_cross_ld in file order: up to cap names into name[] (the context's strings: valid while the
+ * result is); *n_chr (may be NULL) receives their number. */
+int ngsld_cross_ld_chromosomes(ngsld_ctx *ctx, uint64_t cap, const char **name, uint64_t *n_chr);
+/* The last ngsld_cross_ld's arrays of one chosen statistic (field = TSV column 4..7), in the order of ngsld_cross_ld_cells, up
+ * to cap entries each, any pointer may be NULL: sum_micro[] and max_micro[] in micro-units, linked[], mean[]. */
+int ngsld_cross_ld_get(ngsld_ctx *ctx, int field, uint64_t cap, int64_t *sum_micro, int64_t *max_micro, uint64_t *linked, double *mean);
+
 #ifdef __cplusplus
 }
 #endif

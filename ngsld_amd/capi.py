@@ -104,6 +104,7 @@ SYMBOLS = [
     "ngsld_analyze",
     "ngsld_partners", "ngsld_partners_info", "ngsld_partners_get",
     "ngsld_decay_map", "ngsld_decay_map_chromosomes", "ngsld_decay_map_groups", "ngsld_decay_map_bins",
+    "ngsld_cross_ld", "ngsld_cross_ld_cells", "ngsld_cross_ld_chromosomes", "ngsld_cross_ld_get",
 ]
 
 
@@ -154,6 +155,19 @@ class DecayMapStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
                 ("groups", C.c_uint64), ("bins", C.c_uint64), ("group_slots", C.c_uint64), ("bin_slots", C.c_uint64),
                 ("chunks", C.c_uint64), ("pairs_ms", C.c_double), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class CrossLdParams(C.Structure):
+    """ngsld_cross_ld_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("bin_size", C.c_uint64), ("min_maf", C.c_double),
+                ("linked_min", C.c_double), ("min_kb_dist", C.c_double), ("abs_value", C.c_int32), ("within", C.c_int32)]
+
+
+class CrossLdStats(C.Structure):
+    """ngsld_cross_ld_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("lds", C.c_uint32), ("pairs", C.c_uint64), ("pairs_counted", C.c_uint64),
+                ("pairs_cross", C.c_uint64), ("cells", C.c_uint64), ("bins", C.c_uint64), ("chunks", C.c_uint64),
+                ("span_items", C.c_uint64), ("pairs_ms", C.c_double), ("cross_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class BlocksParams(C.Structure):
@@ -452,6 +466,11 @@ def lib() -> C.CDLL:
             L.ngsld_decay_map_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
             L.ngsld_decay_map_groups.argtypes = [vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
             L.ngsld_decay_map_bins.argtypes = [vp, u64, vp, vp, vp, C.POINTER(u64)]
+        if hasattr(L, "ngsld_cross_ld"):
+            L.ngsld_cross_ld.argtypes = [vp, C.POINTER(CrossLdParams), C.POINTER(C.c_char_p), C.POINTER(CrossLdStats)]
+            L.ngsld_cross_ld_cells.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+            L.ngsld_cross_ld_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
+            L.ngsld_cross_ld_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1452,6 +1471,50 @@ class Engine:
                                                cells[f"linked_{f}"].ctypes.data, cells[f"mean_{f}"].ctypes.data))
         cells = {k: v[:nc] for k, v in cells.items()}
         return cells, {k: getattr(st, k) for k, _ in GridStats._fields_ if k != "struct_size"}
+
+    def cross_ld(self, labels: list[str] | None, bin_size: int = 0, ld=("r2",), min_maf: float = 0.0, linked_min: float = 0.5,
+                 abs_value: bool = True, within: bool = True, min_kb_dist: float = 0.0) -> tuple[dict, dict]:
+        """LD across chromosomes of the planned pairs on the device (ngsld_cross_ld, CROSS.md): (cells, stats).  cells holds
+        numpy arrays with one entry per cell with rows, ordered by the bin of the pair's first site, then of its second, the bins
+        numbered consecutively over the chromosomes: "chr1" and "chr2" (the chromosomes' names; with bin_size 0 labels may be
+        None, the names are then "1", "2", ...), "bin1" and "bin2" (the lower breaks b * bin_size of the two windows; 0 with
+        bin_size 0: one bin per chromosome), "n" (counted rows) and per statistic F of ld what Engine.grid gives per cell."""
+        ld = (ld,) if isinstance(ld, str) else tuple(ld)
+        bad = [f for f in ld if f not in DECAY_FIELDS]
+        if bad or not ld:
+            raise ValueError(f"ld must name some of {DECAY_FIELDS}: {bad}")
+        mask = sum(1 << DECAY_FIELDS.index(f) for f in set(ld))
+        arr = None if labels is None else (C.c_char_p * max(len(labels), 1))(*[l.encode() for l in labels])
+        p = CrossLdParams(C.sizeof(CrossLdParams), mask, int(bin_size), float(min_maf), float(linked_min), float(min_kb_dist),
+                          int(bool(abs_value)), int(bool(within)))
+        st = CrossLdStats()
+        st.struct_size = C.sizeof(CrossLdStats)
+        self._check(self._L.ngsld_cross_ld(self._h, C.byref(p), arr, C.byref(st)))
+        nc = int(st.cells)
+        m = max(nc, 1)
+        n_chr = C.c_uint64(0)
+        self._check(self._L.ngsld_cross_ld_chromosomes(self._h, 0, None, C.byref(n_chr)))
+        names = (C.c_char_p * max(int(n_chr.value), 1))()
+        self._check(self._L.ngsld_cross_ld_chromosomes(self._h, int(n_chr.value), names, None))
+        names = np.array([names[k].decode() for k in range(int(n_chr.value))] or [""])
+        i1, i2 = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32)
+        b1, b2 = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+        cells = {"n": np.zeros(m, dtype=np.uint64)}
+        got = C.c_uint64(0)
+        self._check(self._L.ngsld_cross_ld_cells(self._h, m, i1.ctypes.data, b1.ctypes.data, i2.ctypes.data, b2.ctypes.data,
+                                                 cells["n"].ctypes.data, C.byref(got)))
+        assert got.value == nc
+        B = np.uint64(int(bin_size))
+        cells = {"chr1": names[i1], "bin1": b1 * B, "chr2": names[i2], "bin2": b2 * B, **cells}
+        for k, f in enumerate(DECAY_FIELDS):
+            if not (mask >> k) & 1:
+                continue
+            cells[f"sum_{f}"], cells[f"max_{f}"] = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+            cells[f"linked_{f}"], cells[f"mean_{f}"] = np.zeros(m, dtype=np.uint64), np.zeros(m)
+            self._check(self._L.ngsld_cross_ld_get(self._h, 4 + k, m, cells[f"sum_{f}"].ctypes.data, cells[f"max_{f}"].ctypes.data,
+                                                   cells[f"linked_{f}"].ctypes.data, cells[f"mean_{f}"].ctypes.data))
+        cells = {k: v[:nc] for k, v in cells.items()}
+        return cells, {k: getattr(st, k) for k, _ in CrossLdStats._fields_ if k != "struct_size"}
 
     def analyze(self, prune: dict | None = None, decay: dict | None = None, site_ld: dict | None = None,
                 clusters: dict | None = None, grid: dict | None = None, scan: dict | None = None) -> tuple[dict, dict]:

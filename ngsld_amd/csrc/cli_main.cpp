@@ -37,6 +37,9 @@
 //   * --dmap_out FILE / --dmap_fit FILE (new) and the other --dmap_* flags: --decay_out's bins and --decay_fit's fit per
 //     chromosome, or with --dmap_window W per window of W bp, binned on the device (ngsld_decay_map, DECAY_MAP.md); taken out of
 //     argv the same way, no TSV without --out;
+//   * --cross_out FILE (new) and the other --cross_* flags: the whole-genome form of --grid_out -- the rows between every two
+//     chromosomes, or with --cross_bin_size B every two windows of B bp anywhere in the genome, those across two chromosomes
+//     included -- binned on the device (ngsld_cross_ld, CROSS.md); taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -221,6 +224,14 @@ struct DmapArgs {
   double n_ind_v = 0, recomb_rate_v = 1;
   uint64_t fit_min_bins_v = 3;
 } dmap;
+
+// ---- --cross_* (new): LD across chromosomes on the device ----
+struct CrossArgs {
+  bool given = false;  // any --cross_* flag
+  const char *out = nullptr, *bin_size = nullptr, *ld = nullptr, *min_maf = nullptr, *linked_min = nullptr, *min_kb_dist = nullptr;
+  bool is_signed = false, only = false;
+  ngsld_cross_ld_params p{};
+} cross;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -461,6 +472,30 @@ void check_grid_args(const Params &pars) {
   number_arg(__FUNCTION__, "--grid_linked_min", ga->linked_min, &p.linked_min);
   if (pars.in_pos == nullptr) error(__FUNCTION__, "--grid_out needs positions: it cannot run without --pos!");
   one_device(__FUNCTION__, pars, "--grid_out");
+}
+
+// checked as the grid family is; --cross_bin_size is optional (absent: one bin per chromosome)
+void check_cross_args(const Params &pars) {
+  CrossArgs *ca = &cross;
+  if (ca->out == nullptr) error(__FUNCTION__, "the --cross_* options need --cross_out FILE!");
+  if (*ca->out == 0) error(__FUNCTION__, "--cross_out needs a file name!");
+  ngsld_cross_ld_params &p = ca->p;
+  p.struct_size = sizeof(p);
+  p.fields = 8;  // r2
+  p.bin_size = 0;
+  p.min_maf = 0;
+  p.linked_min = 0.5;
+  p.min_kb_dist = 0;
+  p.abs_value = ca->is_signed ? 0 : 1;
+  p.within = ca->only ? 0 : 1;
+  if (ca->bin_size && (!parse_position(ca->bin_size, &p.bin_size) || p.bin_size < 1 || p.bin_size >= (1ull << 31)))
+    error(__FUNCTION__, "--cross_bin_size must be an integer in [1, 2147483647]!");
+  ld_arg(__FUNCTION__, "--cross_ld", ca->ld, &p.fields);
+  finite_arg(__FUNCTION__, "--cross_min_maf", ca->min_maf, &p.min_maf);
+  number_arg(__FUNCTION__, "--cross_linked_min", ca->linked_min, &p.linked_min);
+  finite_arg(__FUNCTION__, "--cross_min_kb_dist", ca->min_kb_dist, &p.min_kb_dist);
+  if (pars.in_pos == nullptr) error(__FUNCTION__, "--cross_out needs positions: it cannot run without --pos!");
+  one_device(__FUNCTION__, pars, "--cross_out");
 }
 
 void check_linked_args(const Params &pars) {
@@ -897,6 +932,49 @@ void write_grid(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *) {
             (unsigned long)st.band, (unsigned long)st.pairs_counted, (unsigned long)st.pairs);
 }
 
+// --cross_out: one line per cell with rows, by the bin of the pair's first site, then of its second (the bins numbered over the
+// chromosomes in file order): both chromosomes, the lower breaks b * B of the two windows (0 without --cross_bin_size), the
+// counted rows, then sum, mean, max and linked of every chosen statistic
+void run_cross(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  CrossArgs &ca = cross;
+  std::vector<const char *> lab(pars.n_sites);
+  for (uint64_t s = 0; s < pars.n_sites; s++) lab[s] = ngsld_host_label(pos, s);
+  ngsld_cross_ld_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_cross_ld(ctx, &ca.p, lab.data(), &st) != NGSLD_OK) error("ngsld_cross_ld", ngsld_last_error(ctx));
+  const uint64_t n = st.cells, B = ca.p.bin_size;
+  const std::vector<int> fields = fields_of(ca.p.fields);
+  const size_t nf = fields.size();
+  uint64_t n_chr = 0;
+  if (ngsld_cross_ld_chromosomes(ctx, 0, nullptr, &n_chr) != NGSLD_OK) error("ngsld_cross_ld_chromosomes", ngsld_last_error(ctx));
+  std::vector<const char *> chr_name(n_chr);
+  if (ngsld_cross_ld_chromosomes(ctx, n_chr, chr_name.data(), nullptr) != NGSLD_OK)
+    error("ngsld_cross_ld_chromosomes", ngsld_last_error(ctx));
+  std::vector<uint32_t> chr1(n), chr2(n);
+  std::vector<uint64_t> b1(n), b2(n), rows(n), linked(nf * n);
+  std::vector<int64_t> sum(nf * n), top(nf * n);
+  std::vector<double> mean(nf * n);
+  if (ngsld_cross_ld_cells(ctx, n, chr1.data(), b1.data(), chr2.data(), b2.data(), rows.data(), nullptr) != NGSLD_OK)
+    error("ngsld_cross_ld_cells", ngsld_last_error(ctx));
+  for (size_t v = 0; v < nf; ++v)
+    if (ngsld_cross_ld_get(ctx, 4 + fields[v], n, sum.data() + v * n, top.data() + v * n, linked.data() + v * n, mean.data() + v * n) !=
+        NGSLD_OK)
+      error("ngsld_cross_ld_get", ngsld_last_error(ctx));
+  FILE *f = fopen(ca.out, "w");
+  if (f == nullptr) error(__FUNCTION__, "cannot open LD across chromosomes output file!");
+  fprintf(f, "chr1\tbin1\tchr2\tbin2\tn");
+  print_summary_header(f, fields);
+  for (uint64_t i = 0; i < n; ++i) {
+    fprintf(f, "%s\t%lu\t%s\t%lu\t%lu", chr_name[chr1[i]], (unsigned long)(b1[i] * B), chr_name[chr2[i]], (unsigned long)(b2[i] * B),
+            (unsigned long)rows[i]);
+    print_summaries(f, nf, n, i, rows[i], sum.data(), mean.data(), top.data(), linked.data());  // (a cell has rows)
+  }
+  if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD across chromosomes output file!");
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD across chromosomes: %lu cells (%lu bins) from %lu of %lu pairs, %lu across chromosomes\n", (unsigned long)n,
+            (unsigned long)st.bins, (unsigned long)st.pairs_counted, (unsigned long)st.pairs, (unsigned long)st.pairs_cross);
+}
+
 // --cluster_out: one line per site of the input, in file order, its cluster or NA; --cluster_table: one line per cluster of
 // at least --cluster_min_size sites, in id order
 ngsld_analysis stage_clusters(const Params &, const ngsld_pos *) {
@@ -1161,6 +1239,8 @@ struct Family {
   void (*run)(ngsld_ctx *, const Params &, const ngsld_pos *);
   void (*write)(ngsld_ctx *, const Params &, const ngsld_pos *);
   const char *timing;          // its line of the NGSLD_TIMING report
+  const char *switch2_name = nullptr;  // a second flag without a value (--cross_only) ...
+  bool *switch2_on = nullptr;          // ... and where it goes
 };
 const Family kFamilies[] = {
     {"prune_",
@@ -1208,6 +1288,11 @@ const Family kFamilies[] = {
       {"dmap_bin_size", &dmap.bin_size}, {"dmap_max_kb_dist", &dmap.max_kb_dist}, {"dmap_min_maf", &dmap.min_maf},
       {"dmap_n_ind", &dmap.n_ind}, {"dmap_recomb_rate", &dmap.recomb_rate}, {"dmap_fit_min_bins", &dmap.fit_min_bins}},
      nullptr, nullptr, &dmap.given, check_dmap_args, nullptr, run_dmap, nullptr, "LD decay map"},  // (a pass of the pair kernels of its own: it is no kind of ngsld_analyze)
+    {"cross_",
+     {{"cross_out", &cross.out}, {"cross_bin_size", &cross.bin_size}, {"cross_ld", &cross.ld}, {"cross_min_maf", &cross.min_maf},
+      {"cross_linked_min", &cross.linked_min}, {"cross_min_kb_dist", &cross.min_kb_dist}},
+     "cross_signed", &cross.is_signed, &cross.given, check_cross_args, nullptr, run_cross, nullptr, "LD across chromosomes",
+     "cross_only", &cross.only},  // (a pass of the pair kernels of its own, as the decay map)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1230,6 +1315,10 @@ void take_flags(int *argc, char **argv, const Family &fam) {
     *fam.given = true;
     if (fam.switch_name != nullptr && key == fam.switch_name && eq == nullptr) {
       *fam.switch_on = true;
+      continue;
+    }
+    if (fam.switch2_name != nullptr && key == fam.switch2_name && eq == nullptr) {
+      *fam.switch2_on = true;
       continue;
     }
     bool known = false;
@@ -1674,7 +1763,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out / --dmap_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out / --dmap_out / --cross_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
@@ -1805,7 +1894,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given && !grid.given && !linked.given && !partners.given && !dmap.given &&  // (the clusters, the grid, the linked pairs, the partners and the decay map need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given && !linked.given && !partners.given && !dmap.given && !cross.given &&  // (the clusters, the grid, the linked pairs, the partners, the decay map and LD across chromosomes need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the

@@ -19,7 +19,11 @@
 //   LINKED_CHUNK_PAIRS, LINKED_FORCE_HOST, SCAN_CHUNK_PAIRS, SCAN_PLANT_DP,
 //   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT, ANALYZE_CHUNK_PAIRS,
 //   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS, PARTNERS_CHUNK_PAIRS, PARTNERS_PLANT_DP,
-//   DMAP_CHUNK_PAIRS, DMAP_LDS_BYTES
+//   DMAP_CHUNK_PAIRS, DMAP_LDS_BYTES,
+//   CROSS_CHUNK_PAIRS, CROSS_SPAN_ITEMS, CROSS_PLANT_DP
+// CROSS_CHUNK_PAIRS=n: ngsld_cross_ld's chunks of rows hold about n pairs instead of 2^24 (cross.hip).  CROSS_SPAN_ITEMS=M: a
+// wavefront of its kernel carries its current cell over M consecutive items instead of the measured default (CROSS.md); 1 is one
+// set of atomics per run, grid.hip's global form.  CROSS_PLANT_DP=R:X: SCAN_PLANT_DP for ngsld_cross_ld.
 // DMAP_CHUNK_PAIRS=n: ngsld_decay_map's chunks of rows hold about n pairs instead of 2^24 (decay_map.hip).  DMAP_LDS_BYTES=n: its
 // per-workgroup LDS budget for the home group's bins, at most 64 KiB; 0 sends every add to global memory.
 // PARTNERS_PLANT_DP=R:X: SCAN_PLANT_DP for ngsld_partners (partners.hip), whose refusal begins at 2^31 micro-units.

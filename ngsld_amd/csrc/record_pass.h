@@ -5,7 +5,8 @@
 // site filter's arrays (SiteFilter), the chunk loop (RecordPass), the refusals of a value or a sum out of range, the sum / max /
 // linked accumulators of site LD and the grid, a label's CHR:pos.  The kernels share nothing of it: their filters differ -- but for
 // ngsld_decay and ngsld_decay_map (decay_map.hip), whose filter is one and which run one kernel (ld_decay_bins.h).
-// (ngsld_scan uses the site filter, the chunk loop, the two refusals and the guard of the sums.)
+// (ngsld_scan uses the site filter, the chunk loop, the two refusals and the guard of the sums; ngsld_cross_ld (cross.hip) all of
+// it, as the grid does.)
 // The chunk loop takes a list of passes: the pairs of a chunk run once and every pass of the list reads them (ngsld_analyze,
 // analyze.hip); the six passes it can list are AnalysisPass objects, and their single calls are a list of one.
 // Host code; the definitions are in record_pass.hip.

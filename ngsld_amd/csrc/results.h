@@ -1,5 +1,5 @@
 // results.h -- what the on-device analyses leave in the context until a getter copies it out: one struct per analysis with the test
-// its getters make (valid) and a clear of its own; Results holds the eight and the one rule of what a new plan makes stale.
+// its getters make (valid) and a clear of its own; Results holds the nine and the one rule of what a new plan makes stale.
 #pragma once  // (host code; engine.h includes it behind DevBuf)
 
 // rank of TSV column `field` (4..7) among the chosen fields (1 r2_ExpG, 2 D, 4 D', 8 r2), -1 when it was not chosen
@@ -98,12 +98,24 @@ struct DecayMapResult {
   bool valid() const { return fields != 0; }  void clear() { *this = DecayMapResult(); }
 };
 
+// ngsld_cross_ld (cross.hip): the chromosomes in file order, then per cell with rows -- by the consecutive bin of the first site,
+// then of the second -- the chromosome and bin of both sites and its rows, and per chosen field [rank][cell] what GridResult holds
+struct CrossResult {
+  uint32_t fields = 0;
+  std::vector<std::string> chr_name;
+  std::vector<uint32_t> chr1, chr2;
+  std::vector<uint64_t> b1, b2, n, linked;
+  std::vector<int64_t> sum, max;
+  std::vector<double> mean;
+  bool valid() const { return fields != 0; }  void clear() { *this = CrossResult(); }
+};
+
 // The lifetime rule, stated here alone.  An analysis clears its own store when it begins and touches no other.  ngsld_plan and every
-// ngsld_set_* call invalidate_for_new_plan: seven stores hold values per site, region, cell or group of the plan that made them, which a new
+// ngsld_set_* call invalidate_for_new_plan: eight stores hold values per site, region, cell or group of the plan that made them, which a new
 // matrix, setting or plan makes stale.  The decay bins are indexed by distance, not by site: they stay until the next ngsld_decay.
 struct Results {
   DecayResult decay;  // (by distance: a new plan leaves it)
   BlocksResult blocks; SiteLdResult site_ld; ClustersResult clusters; GridResult grid; ScanResult scan; PartnersResult partners;
-  DecayMapResult decay_map;
-  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); decay_map.clear(); }
+  DecayMapResult decay_map; CrossResult cross;
+  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); decay_map.clear(); cross.clear(); }
 };
