@@ -609,6 +609,57 @@ int ngsld_clusters_table(ngsld_ctx *ctx, uint64_t min_size, uint64_t cap, uint32
                          uint32_t *last, uint64_t *span, uint64_t *edges, int64_t *sum_micro, double *mean, double *density,
                          uint64_t *n);
 
+/* ---- LD tree on the device (TREE.md) ----------------------------------------------------------------------------------------
+ * The single-linkage tree of the sites: the maximum spanning forest of the graph ngsld_clusters unites, kept on the device while
+ * the rows stream past -- without the TSV and without the graph's edge list.  Nodes and edges are those of ngsld_clusters.  Edge
+ * e comes before edge f iff q_e > q_f (the printed value in micro-units, |q| with abs_value), or the q are equal and
+ * s1_e < s1_f, or those are equal too and s2_e < s2_f; the edges taken in that order, an edge is kept iff its two ends lie in
+ * different trees so far.  The kept edges, in that order, are the merges 1..M, M = nodes - clusters at the floor min_weight; every
+ * cut of them at a floor t >= min_weight is what ngsld_clusters gives at min_weight = t (ngsld_ld_tree_cut).  The rule is in
+ * TREE.md.  Both structs start with struct_size, as the pruning structs do. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_ld_tree_params) */
+  int32_t field;              /* TSV column of the edge value: 4 r2_ExpG, 5 D, 6 D', 7 r2 (default) */
+  double max_kb_dist;         /* an edge needs dist <= max_kb_dist * 1000 (INFINITY: no limit, the default) */
+  double min_maf;             /* an edge needs maf1 >= min_maf and maf2 >= min_maf, as printed (default 0) */
+  double min_weight;          /* an edge needs value >= min_weight (default 0.1; a value equal to it is an edge): the lowest cut */
+  int32_t abs_value;          /* != 0 (default): |value|; 0: the signed value */
+  int32_t reserved;           /* 0 */
+} ngsld_ld_tree_params;
+
+typedef struct {
+  uint32_t struct_size;       /* sizeof(ngsld_ld_tree_stats) */
+  uint32_t reserved;          /* 0 */
+  uint64_t pairs;             /* pairs computed */
+  uint64_t nodes;             /* sites that are one end of an emitted pair */
+  uint64_t edges;             /* pairs that are edges: the candidates that passed */
+  uint64_t merges;            /* edges of the forest */
+  uint64_t clusters;          /* clusters at the floor, singletons included: nodes - merges */
+  uint64_t chunks;            /* chunks of rows the pairs ran in */
+  uint64_t rounds;            /* rounds of all the reduces (a chunk without a candidate has no reduce) */
+  uint64_t max_rounds;        /* the most rounds of one reduce: at most ceil(log2(n_sites)) + 1, whatever the diameter */
+  uint64_t displaced;         /* forest edges that a later chunk's reduce dropped */
+  double pairs_ms, edges_ms, reduce_ms, finish_ms, total_ms;  /* pair kernels + replay, the candidates kernel (kernel time), the
+                                                                 reduces (wall time), copy back + the host's pass, the whole call */
+} ngsld_ld_tree_stats;
+
+/* The tree after ngsld_plan; the context keeps it until the next ngsld_ld_tree, ngsld_plan or ngsld_set_*.  stats may be NULL.
+ * NGSLD_ERR_UNSUPPORTED for non-integer position gaps or a value of 2^38 micro-units or more (|x| >= 274877.906944, naming the
+ * pair); nothing is summed, so no sum can wrap. */
+int ngsld_ld_tree(ngsld_ctx *ctx, const ngsld_ld_tree_params *params, ngsld_ld_tree_stats *stats);
+/* The last ngsld_ld_tree's merges in rule order, up to cap rows into each array that is not NULL; *n (may be NULL) receives the
+ * number of merges.  Merge k (from 1) joins the clusters that held s1[k-1] and s2[k-1] through the edge of q_micro[k-1]
+ * micro-units and dist[k-1] bp (what the TSV prints); left[] and right[] name those two clusters as R's hclust$merge does --
+ * -(site index + 1) for a single site, the number of the merge that made it otherwise --; size[] is the number of sites after
+ * the merge, first[] and last[] the smallest and largest site index of the merged cluster. */
+int ngsld_ld_tree_merges(ngsld_ctx *ctx, uint64_t cap, uint32_t *s1, uint32_t *s2, int64_t *q_micro, uint64_t *dist, int64_t *left,
+                         int64_t *right, uint32_t *size, uint32_t *first, uint32_t *last, uint64_t *n);
+/* The clusters of the last ngsld_ld_tree at the floor t: cluster[] (n_sites entries, may be NULL) and *n_clusters (may be NULL)
+ * are what ngsld_clusters_sites and its stats give at min_weight = t with the other parameters equal -- ids 1, 2, ... in
+ * increasing order of the smallest site, singletons included, 0 for a site that is not a node.  A host pass over the stored
+ * merges: no device work.  NGSLD_ERR_INVALID for a NaN or a t below the tree's min_weight. */
+int ngsld_ld_tree_cut(ngsld_ctx *ctx, double t, uint32_t *cluster, uint64_t *n_clusters);
+
 /* ---- LD grid on the device (GRID.md) ----------------------------------------------------------------------------------------
  * The TSV this context's plan would print, binned into a heat map along each chromosome -- without the TSV: the pairs run again
  * chunk by chunk into device records (every pair kernel, the exact-order replay included) and a kernel adds every counted row to

@@ -105,6 +105,7 @@ SYMBOLS = [
     "ngsld_partners", "ngsld_partners_info", "ngsld_partners_get",
     "ngsld_decay_map", "ngsld_decay_map_chromosomes", "ngsld_decay_map_groups", "ngsld_decay_map_bins",
     "ngsld_cross_ld", "ngsld_cross_ld_cells", "ngsld_cross_ld_chromosomes", "ngsld_cross_ld_get",
+    "ngsld_ld_tree", "ngsld_ld_tree_merges", "ngsld_ld_tree_cut",
 ]
 
 
@@ -209,6 +210,20 @@ class ClustersStats(C.Structure):
                 ("edges", C.c_uint64), ("clusters", C.c_uint64), ("clusters_multi", C.c_uint64), ("largest", C.c_uint64),
                 ("chunks", C.c_uint64), ("union_launches", C.c_uint64), ("pairs_ms", C.c_double), ("union_ms", C.c_double),
                 ("finish_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class TreeParams(C.Structure):
+    """ngsld_ld_tree_params (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("field", C.c_int32), ("max_kb_dist", C.c_double), ("min_maf", C.c_double),
+                ("min_weight", C.c_double), ("abs_value", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TreeStats(C.Structure):
+    """ngsld_ld_tree_stats (include/ngsld.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("nodes", C.c_uint64),
+                ("edges", C.c_uint64), ("merges", C.c_uint64), ("clusters", C.c_uint64), ("chunks", C.c_uint64),
+                ("rounds", C.c_uint64), ("max_rounds", C.c_uint64), ("displaced", C.c_uint64), ("pairs_ms", C.c_double),
+                ("edges_ms", C.c_double), ("reduce_ms", C.c_double), ("finish_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class GridParams(C.Structure):
@@ -471,6 +486,10 @@ def lib() -> C.CDLL:
             L.ngsld_cross_ld_cells.argtypes = [vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
             L.ngsld_cross_ld_chromosomes.argtypes = [vp, u64, C.POINTER(C.c_char_p), C.POINTER(u64)]
             L.ngsld_cross_ld_get.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp]
+        if hasattr(L, "ngsld_ld_tree"):
+            L.ngsld_ld_tree.argtypes = [vp, C.POINTER(TreeParams), C.POINTER(TreeStats)]
+            L.ngsld_ld_tree_merges.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
+            L.ngsld_ld_tree_cut.argtypes = [vp, C.c_double, vp, C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -1419,6 +1438,34 @@ class Engine:
         self._check(self._L.ngsld_clusters_table(self._h, int(min_size), m, *(table[k].ctypes.data for k in kinds), C.byref(rows)))
         table = {k: v[:int(rows.value)] for k, v in table.items()}
         return ids[:self.n_sites], table, {k: getattr(st, k) for k, _ in ClustersStats._fields_ if k not in ("struct_size", "reserved")}
+
+    def ld_tree(self, field: int = 7, min_weight: float = 0.1, max_kb_dist: float = float("inf"), min_maf: float = 0.0,
+                abs_value: bool = True) -> tuple[dict, dict]:
+        """The single-linkage LD tree of the planned pairs on the device (ngsld_ld_tree, TREE.md): (merges, stats).  merges holds
+        numpy arrays with one entry per merge, in rule order: "s1", "s2" (the edge's sites), "q" (int64 micro-units: value *
+        10^6), "dist", "left" and "right" (R's hclust$merge convention: -(site index + 1) for a single site, else the number of
+        the merge that made the cluster), "size", "first" and "last".  Engine.ld_tree_cut gives the clusters at any floor >=
+        min_weight without another run."""
+        p = TreeParams(C.sizeof(TreeParams), int(field), float(max_kb_dist), float(min_maf), float(min_weight), int(bool(abs_value)), 0)
+        st = TreeStats()
+        st.struct_size = C.sizeof(TreeStats)
+        self._check(self._L.ngsld_ld_tree(self._h, C.byref(p), C.byref(st)))
+        rows = C.c_uint64(0)
+        self._check(self._L.ngsld_ld_tree_merges(self._h, 0, None, None, None, None, None, None, None, None, None, C.byref(rows)))
+        m = max(int(rows.value), 1)
+        kinds = dict(s1=np.uint32, s2=np.uint32, q=np.int64, dist=np.uint64, left=np.int64, right=np.int64, size=np.uint32,
+                     first=np.uint32, last=np.uint32)
+        merges = {k: np.zeros(m, dtype=t) for k, t in kinds.items()}
+        self._check(self._L.ngsld_ld_tree_merges(self._h, m, *(merges[k].ctypes.data for k in kinds), C.byref(rows)))
+        merges = {k: v[:int(rows.value)] for k, v in merges.items()}
+        return merges, {k: getattr(st, k) for k, _ in TreeStats._fields_ if k not in ("struct_size", "reserved")}
+
+    def ld_tree_cut(self, t: float) -> np.ndarray:
+        """The clusters of the last ld_tree at the floor t >= its min_weight (ngsld_ld_tree_cut): every site's cluster id, what
+        Engine.clusters gives at min_weight = t with the other parameters equal.  No device work."""
+        ids = np.zeros(max(self.n_sites, 1), dtype=np.uint32)
+        self._check(self._L.ngsld_ld_tree_cut(self._h, float(t), ids.ctypes.data, None))
+        return ids[:self.n_sites]
 
     def grid(self, labels: list[str] | None, bin_size: int, ld=("r2",), max_kb_dist: float = float("inf"), min_maf: float = 0.0,
              linked_min: float = 0.5, abs_value: bool = True) -> tuple[dict, dict]:

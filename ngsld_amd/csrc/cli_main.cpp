@@ -40,6 +40,10 @@
 //   * --cross_out FILE (new) and the other --cross_* flags: the whole-genome form of --grid_out -- the rows between every two
 //     chromosomes, or with --cross_bin_size B every two windows of B bp anywhere in the genome, those across two chromosomes
 //     included -- binned on the device (ngsld_cross_ld, CROSS.md); taken out of argv the same way, no TSV without --out;
+//   * --tree_out FILE (new) and the other --tree_* flags: the single-linkage tree of the sites -- the maximum spanning forest of
+//     the graph --cluster_out unites, every merge in order of falling LD -- kept on the device while the rows stream past, and
+//     with --tree_cut T1,T2,... --tree_cut_out FILE the clusters at those floors from that one run (ngsld_ld_tree, TREE.md);
+//     taken out of argv the same way, no TSV without --out;
 #include <getopt.h>
 #include <zlib.h>
 #include <sys/stat.h>
@@ -232,6 +236,17 @@ struct CrossArgs {
   bool is_signed = false, only = false;
   ngsld_cross_ld_params p{};
 } cross;
+
+// ---- --tree_* (new): the single-linkage LD tree on the device ----
+struct TreeArgs {
+  bool given = false;  // any --tree_* flag
+  const char *out = nullptr, *field = nullptr, *min_weight = nullptr, *max_kb_dist = nullptr, *min_maf = nullptr, *cut = nullptr,
+             *cut_out = nullptr;
+  bool is_signed = false;
+  std::vector<std::string> cut_text;  // the floors of --tree_cut as they were typed
+  std::vector<double> cut_v;
+  ngsld_ld_tree_params p{};
+} tree;
 
 bool parse_double(const char *txt, double *out) {
   char *end = nullptr;
@@ -450,6 +465,42 @@ void check_cluster_args(const Params &pars) {
     ca->min_size_v = v;
   }
   one_device(__FUNCTION__, pars, "--cluster_out");
+}
+
+void check_tree_args(const Params &pars) {
+  TreeArgs *ta = &tree;
+  if (ta->out == nullptr && ta->cut_out == nullptr) error(__FUNCTION__, "the --tree_* options need --tree_out FILE or --tree_cut_out FILE!");
+  if (ta->out != nullptr && *ta->out == 0) error(__FUNCTION__, "--tree_out needs a file name!");
+  if (ta->cut_out != nullptr && *ta->cut_out == 0) error(__FUNCTION__, "--tree_cut_out needs a file name!");
+  if (ta->cut_out != nullptr && ta->cut == nullptr) error(__FUNCTION__, "--tree_cut_out needs the floors to cut at: --tree_cut T1,T2,...!");
+  if (ta->cut != nullptr && ta->cut_out == nullptr) error(__FUNCTION__, "--tree_cut needs --tree_cut_out FILE!");
+  ngsld_ld_tree_params &p = ta->p;
+  p.struct_size = sizeof(p);
+  p.field = 7;
+  p.max_kb_dist = INFINITY;
+  p.min_maf = 0;
+  p.min_weight = 0.1;
+  p.abs_value = ta->is_signed ? 0 : 1;
+  column_arg(__FUNCTION__, "--tree_field", ta->field, &p.field);
+  number_arg(__FUNCTION__, "--tree_min_weight", ta->min_weight, &p.min_weight);
+  dist_arg(__FUNCTION__, "--tree_max_kb_dist", ta->max_kb_dist, &p.max_kb_dist);
+  finite_arg(__FUNCTION__, "--tree_min_maf", ta->min_maf, &p.min_maf);
+  if (ta->cut) {  // a comma-separated list of floors, none below the tree's own
+    const std::string txt = ta->cut;
+    size_t b = 0;
+    while (true) {
+      const size_t e = std::min(txt.find(',', b), txt.size());
+      const std::string one = txt.substr(b, e - b);
+      double v = 0;
+      if (!parse_double(one.c_str(), &v)) error(__FUNCTION__, "--tree_cut must be a comma-separated list of numbers!");
+      if (v < p.min_weight) error(__FUNCTION__, "--tree_cut cannot go below --tree_min_weight: the tree holds no edge under it!");
+      ta->cut_text.push_back(one);
+      ta->cut_v.push_back(v);
+      if (e == txt.size()) break;
+      b = e + 1;
+    }
+  }
+  one_device(__FUNCTION__, pars, "--tree_out");
 }
 
 void check_grid_args(const Params &pars) {
@@ -1137,6 +1188,67 @@ void run_partners(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
             (unsigned long)st.entries, (unsigned long)st.sites_with_partners, k, (unsigned long)st.rows_counted, (unsigned long)st.pairs);
 }
 
+// --tree_out: one line per merge, in rule order (the merge and size columns load as R's hclust$merge and the sizes); --tree_cut_out:
+// one line per site of the input, in file order, its cluster at every floor of --tree_cut or NA
+void run_tree(ngsld_ctx *ctx, const Params &pars, const ngsld_pos *pos) {
+  TreeArgs &ta = tree;
+  const uint64_t n = pars.n_sites;
+  ngsld_ld_tree_stats st{};
+  st.struct_size = sizeof(st);
+  if (ngsld_ld_tree(ctx, &ta.p, &st) != NGSLD_OK) error("ngsld_ld_tree", ngsld_last_error(ctx));
+  if (ta.out) {
+    const uint64_t rows = st.merges;
+    std::vector<uint32_t> s1(rows), s2(rows), size(rows), first(rows), last(rows);
+    std::vector<int64_t> q(rows), left(rows), right(rows);
+    std::vector<uint64_t> dist(rows);
+    if (ngsld_ld_tree_merges(ctx, rows, s1.data(), s2.data(), q.data(), dist.data(), left.data(), right.data(), size.data(), first.data(),
+                             last.data(), nullptr) != NGSLD_OK)
+      error("ngsld_ld_tree_merges", ngsld_last_error(ctx));
+    FILE *f = fopen(ta.out, "w");
+    if (f == nullptr) error(__FUNCTION__, "cannot open LD tree output file!");
+    fprintf(f, "merge\tsite1\tsite2\tweight\tdist\tleft\tright\tsize\tfirst\tlast\n");
+    for (uint64_t k = 0; k < rows; ++k) {
+      fprintf(f, "%lu\t", (unsigned long)(k + 1));
+      print_site(f, pos, s1[k]);
+      fprintf(f, "\t");
+      print_site(f, pos, s2[k]);
+      print_micro(f, q[k]);
+      fprintf(f, "\t%lu\t%ld\t%ld\t%u\t", (unsigned long)dist[k], (long)left[k], (long)right[k], size[k]);
+      print_site(f, pos, first[k]);
+      fprintf(f, "\t");
+      print_site(f, pos, last[k]);
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD tree output file!");
+  }
+  if (ta.cut_out) {
+    const size_t cuts = ta.cut_v.size();
+    std::vector<uint32_t> id(cuts * n);
+    for (size_t k = 0; k < cuts; ++k)
+      if (ngsld_ld_tree_cut(ctx, ta.cut_v[k], id.data() + k * n, nullptr) != NGSLD_OK) error("ngsld_ld_tree_cut", ngsld_last_error(ctx));
+    FILE *f = fopen(ta.cut_out, "w");
+    if (f == nullptr) error(__FUNCTION__, "cannot open LD tree cuts output file!");
+    fprintf(f, "site");
+    for (const std::string &t : ta.cut_text) fprintf(f, "\t%s", t.c_str());
+    fprintf(f, "\n");
+    for (uint64_t s = 0; s < n; ++s) {
+      print_site(f, pos, s);
+      for (size_t k = 0; k < cuts; ++k) {
+        if (id[k * n + s] == 0)
+          fprintf(f, "\tNA");
+        else
+          fprintf(f, "\t%u", id[k * n + s]);
+      }
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) error(__FUNCTION__, "cannot write LD tree cuts output file!");
+  }
+  if (pars.verbose >= 1)
+    fprintf(stderr, "==> LD tree: %lu merges of %lu nodes (%lu clusters at the floor), %lu edges of %lu pairs, %lu rounds in %lu chunks\n",
+            (unsigned long)st.merges, (unsigned long)st.nodes, (unsigned long)st.clusters, (unsigned long)st.edges, (unsigned long)st.pairs,
+            (unsigned long)st.rounds, (unsigned long)st.chunks);
+}
+
 int write_blocks_text(void *user, const char *text, uint64_t len) {
   return fwrite(text, 1, len, static_cast<FILE *>(user)) == len ? 0 : 1;
 }
@@ -1293,6 +1405,10 @@ const Family kFamilies[] = {
       {"cross_linked_min", &cross.linked_min}, {"cross_min_kb_dist", &cross.min_kb_dist}},
      "cross_signed", &cross.is_signed, &cross.given, check_cross_args, nullptr, run_cross, nullptr, "LD across chromosomes",
      "cross_only", &cross.only},  // (a pass of the pair kernels of its own, as the decay map)
+    {"tree_",
+     {{"tree_out", &tree.out}, {"tree_field", &tree.field}, {"tree_min_weight", &tree.min_weight}, {"tree_max_kb_dist", &tree.max_kb_dist},
+      {"tree_min_maf", &tree.min_maf}, {"tree_cut", &tree.cut}, {"tree_cut_out", &tree.cut_out}},
+     "tree_signed", &tree.is_signed, &tree.given, check_tree_args, nullptr, run_tree, nullptr, "LD tree"},  // (a pass of the pair kernels of its own: a forest that persists across its chunks)
 };
 
 // Takes a family's flags (one or two dashes) out of argv.  The values are checked once the reference's own arguments have been.
@@ -1763,7 +1879,7 @@ int main(int argc, char **argv) {
       any_family = true;
       fam.check(pars);
     }
-  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out / --dmap_out / --cross_out without --out: no TSV
+  // --prune_out / --decay_out / --blocks_out / --site_out / --cluster_out / --cluster_table / --grid_out / --linked_out / --scan_out / --partners_out / --dmap_out / --cross_out / --tree_out without --out: no TSV
   const bool write_tsv = !any_family || pars.out != NULL;
 
   // ---- check input files (ngsLD.cpp:41-57) ----
@@ -1894,7 +2010,7 @@ int main(int argc, char **argv) {
       slab_sites = ngsld_sites_for_budget(pars.n_ind, budget, 1);  // (slabs without room for the store before none at all)
       if (slab_sites < 2) error(__FUNCTION__, "the device memory budget is too small for this number of individuals");
     }
-  } else if (!cluster.given && !grid.given && !linked.given && !partners.given && !dmap.given && !cross.given &&  // (the clusters, the grid, the linked pairs, the partners, the decay map and LD across chromosomes need the matrix resident: a job that fits is not cut only to overlap its read)
+  } else if (!cluster.given && !grid.given && !linked.given && !partners.given && !dmap.given && !cross.given && !tree.given &&  // (the clusters, the grid, the linked pairs, the partners, the decay map, LD across chromosomes and the tree need the matrix resident: a job that fits is not cut only to overlap its read)
              pars.in_bin && (pars.max_kb_dist > 0 || pars.max_snp_dist > 0) && (uint64_t)st.st_size >= (4ull << 30) &&
              !(getenv("NGSLD_PIPELINE") && strcmp(getenv("NGSLD_PIPELINE"), "0") == 0)) {
     // a large windowed job that fits is still cut into about six slabs, only to overlap the file read and the

@@ -20,7 +20,10 @@
 //   PRUNE_CHUNK_PAIRS, RECORD_SLICE_ITEMS, SUM_WRAP_LIMIT, ANALYZE_CHUNK_PAIRS,
 //   FIRST_STEP, PAIR_MOMENTS, MOMENTS_PAIRS, PARTNERS_CHUNK_PAIRS, PARTNERS_PLANT_DP,
 //   DMAP_CHUNK_PAIRS, DMAP_LDS_BYTES,
-//   CROSS_CHUNK_PAIRS, CROSS_SPAN_ITEMS, CROSS_PLANT_DP
+//   CROSS_CHUNK_PAIRS, CROSS_SPAN_ITEMS, CROSS_PLANT_DP,
+//   TREE_CHUNK_PAIRS, TREE_PLANT
+// TREE_CHUNK_PAIRS=n: ngsld_ld_tree's chunks of rows hold about n pairs instead of 2^24 (tree.hip).  TREE_PLANT=R:X: SCAN_PLANT_DP for
+// ngsld_ld_tree, into the field the call reads.
 // CROSS_CHUNK_PAIRS=n: ngsld_cross_ld's chunks of rows hold about n pairs instead of 2^24 (cross.hip).  CROSS_SPAN_ITEMS=M: a
 // wavefront of its kernel carries its current cell over M consecutive items instead of the measured default (CROSS.md); 1 is one
 // set of atomics per run, grid.hip's global form.  CROSS_PLANT_DP=R:X: SCAN_PLANT_DP for ngsld_cross_ld.

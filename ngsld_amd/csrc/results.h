@@ -1,5 +1,5 @@
 // results.h -- what the on-device analyses leave in the context until a getter copies it out: one struct per analysis with the test
-// its getters make (valid) and a clear of its own; Results holds the nine and the one rule of what a new plan makes stale.
+// its getters make (valid) and a clear of its own; Results holds the ten and the one rule of what a new plan makes stale.
 #pragma once  // (host code; engine.h includes it behind DevBuf)
 
 // rank of TSV column `field` (4..7) among the chosen fields (1 r2_ExpG, 2 D, 4 D', 8 r2), -1 when it was not chosen
@@ -110,12 +110,23 @@ struct CrossResult {
   bool valid() const { return fields != 0; }  void clear() { *this = CrossResult(); }
 };
 
+// ngsld_ld_tree (tree.hip): the merges in rule order, the floor they were built at and the node marks a cut needs
+struct TreeResult {
+  bool filled = false;  // (a result may hold no merge at all)
+  double min_weight = 0;
+  std::vector<uint8_t> node;
+  std::vector<uint32_t> s1, s2, size, first, last;
+  std::vector<int64_t> q, left, right;
+  std::vector<uint64_t> dist;
+  bool valid() const { return filled; }  void clear() { *this = TreeResult(); }
+};
+
 // The lifetime rule, stated here alone.  An analysis clears its own store when it begins and touches no other.  ngsld_plan and every
 // ngsld_set_* call invalidate_for_new_plan: eight stores hold values per site, region, cell or group of the plan that made them, which a new
 // matrix, setting or plan makes stale.  The decay bins are indexed by distance, not by site: they stay until the next ngsld_decay.
 struct Results {
   DecayResult decay;  // (by distance: a new plan leaves it)
   BlocksResult blocks; SiteLdResult site_ld; ClustersResult clusters; GridResult grid; ScanResult scan; PartnersResult partners;
-  DecayMapResult decay_map; CrossResult cross;
-  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); decay_map.clear(); cross.clear(); }
+  DecayMapResult decay_map; CrossResult cross; TreeResult tree;
+  void invalidate_for_new_plan() { blocks.clear(); site_ld.clear(); clusters.clear(); grid.clear(); scan.clear(); partners.clear(); decay_map.clear(); cross.clear(); tree.clear(); }
 };
